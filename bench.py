@@ -17,6 +17,9 @@ At N=1 the whole iteration is ONE engine call (mb_bert_train_step: step prologue
 
 Prints ONE JSON line (rank 0) with the contract's keys plus
   step_ms_median / p10 / p90 : per-step GPU time from HIP events recorded after every step
+A plain run does only that: set up, warm up, time --steps steps, (--dump-outputs DIR: write what the last timed step computed
+as DIR/*.npy), print.  --full then goes on measuring, after the timed steps, and adds
+  value_with_per_step_h2d, host_call_ms_per_step, comm_* : the host-fed loop, host cost per call, exchange exposure (N > 1)
   roofline       : the kernel with the largest share of the step -- the per-layer grouped weight-gradient GEMM (MFMA-bound) or the
                    optimizer (HBM-bound) -- timed INSIDE the step with HIP events on the stream it runs on; both are always printed
                    (roofline_mfma, roofline_adamw); HBM-side traffic is REPLAYED from the committed PMC pass (profiles/pmc_traffic.json)
@@ -70,7 +73,39 @@ def parse():
     p.add_argument("--secondary", type=int, default=1,
                    help="1 (default, N = 1, headline workload only): also measure BASELINE.json configs[3] (MAG-XLNet, B=48, L=50) and the per-GPU "
                         "shape of configs[4] (MAG-BERT MOSEI V=35, B=32, L=128) in the same process and append them as `secondary`")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure everything beyond the headline: the host-fed rate (value_with_per_step_h2d), "
+                        "in-step kernel timings, host cost per call, the gradient exchange's exposure (data parallel) and -- each switchable "
+                        "off with its own option above -- roofline, secondary workloads, one epoch and the CPU baseline.  Without it a run "
+                        "sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (float32): its loss, and a fixed seeded sample of the "
+                        "updated flat parameters and AdamW moments.  Inputs are the same in every run; the outputs carry the run-to-run "
+                        "noise of the fp32 gradient atomics unless MB_DETERMINISTIC=1 is set")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_SAMPLE = 1 << 20           # elements per sampled flat buffer (4 MB each in float32)
+
+
+def dump_outputs(d, model, loss):
+    """The arrays a caller of the timed step holds after its last call: the returned loss and the model's updated parameters
+    (+ the optimizer's moments), the flat buffers as the same seeded sample of DUMP_SAMPLE indices in every run."""
+    os.makedirs(d, exist_ok=True)
+    core = model._core
+    n = int(core.params.numel())
+    idx = np.sort(np.random.default_rng(20240917).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx_t = torch.from_numpy(idx).to(core.params.device)
+    out = {"loss": loss.detach().reshape(-1)[:1], "params_sample": core.params[idx_t]}
+    for name, attr in (("adam_m_sample", "_adam_m"), ("adam_v_sample", "_adam_v")):
+        t = getattr(core, attr, None)
+        if t is not None:
+            out[name] = t[idx_t]
+    for name, t in out.items():
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 def make_batches(n, B, L, V, A, seed, layout="bert"):
@@ -690,6 +725,71 @@ def cpu_info():
     return {"cpu_model": model, "os_cpu_count": os.cpu_count(), "physical_cores": phys}
 
 
+def full_step_extras(model, opt, sch, resident, nb, use_graph, single_call, dp, dp_call):
+    """--full: steps beyond the timed region that measure what the headline does not need -> (in-step wgrad us, in-step AdamW us,
+    host ms per call, exposed exchange ms, comm stats, steps run)."""
+    # in-step duration of the two largest kernels of the step -- the per-layer grouped weight-gradient GEMM and the optimizer -- from
+    # HIP events the engine records around them on the stream they run on (profiling events cannot live inside a captured graph:
+    # these steps run the same kernel sequence launch by launch)
+    wgrad_in_step_us = adamw_in_step_us = None
+    comm_exposed_ms = None
+    n3 = 0
+    try:
+        import ctypes as C
+        from bert_multimodal_transformer_amd import _lib
+        core = model._core
+        fn = lambda name: getattr(_lib.lib(), "mb_%s_%s" % (core.kind, name))
+        _lib.check(fn("set_profiling")(core.handle, 1))
+        acc, acc_a = [], []
+        for i in range(7):
+            ids, vis, aco, mask, seg, lab = resident[i % nb]
+            model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
+            sch.step()
+            torch.cuda.synchronize()
+            v = C.c_float()
+            _lib.check(fn("profile_wgrad_us")(core.handle, C.byref(v)))
+            acc.append(v.value)
+            if single_call:
+                _lib.check(fn("profile_adamw_us")(core.handle, C.byref(v)))
+                acc_a.append(v.value)
+        _lib.check(fn("set_profiling")(core.handle, 0))
+        wgrad_in_step_us = float(np.median(acc[1:]))
+        adamw_in_step_us = float(np.median(acc_a[1:])) if acc_a else None
+        n3 = 7
+    except Exception as ex:          # MB_GROUP_WGRAD=0 (separate launches): no grouped kernel to time
+        print("note: in-step kernel timing unavailable (%s)" % ex, file=sys.stderr)
+    # host cost of ONE step call with an empty queue (host_enqueue_ms_per_step above is wall time of the enqueue loop: once the host
+    # is a few steps ahead it blocks on the launch queue's depth and the figure approaches the GPU time -- it says nothing about the host)
+    host_call = []
+    for i in range(6):
+        ids, vis, aco, mask, seg, lab = resident[i % nb]
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
+        sch.step()
+        host_call.append(time.perf_counter() - th)
+    torch.cuda.synchronize()
+    host_call_ms = float(np.median(host_call[1:])) * 1e3
+    n3 += 6
+    comm_stats = None
+    if dp is not None:
+        if dp_call:          # five more steps with the comm object's timing events on: the compute stream's stalls on the exchange
+            dp.comm.set_timing(True)
+            ex = []
+            for i in range(5):
+                ids, vis, aco, mask, seg, lab = resident[i % nb]
+                model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
+                sch.step()
+                ex.append(dp.exposed_ms())
+            dp.comm.set_timing(False)
+            comm_exposed_ms = float(np.median(ex))
+            comm_stats = dp.comm.stats()
+            n3 += 5
+        else:
+            comm_exposed_ms = dp.exposed_ms()
+    return wgrad_in_step_us, adamw_in_step_us, host_call_ms, comm_exposed_ms, comm_stats, n3
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -736,7 +836,6 @@ def main():
         model = MAG_BertForSequenceClassification(BertConfig(num_labels=1), MultimodalConfig(1.0, 0.5), visual_dim=V,
                                                   acoustic_dim=A, compute_dtype=cdt)
     opt = AdamW(optimizer_grouped_parameters(model), lr=1e-5)
-    total_steps = a.steps + a.warmup
     sch = get_linear_schedule_with_warmup(opt, num_warmup_steps=0.1 * 1040, num_training_steps=1040)
     dp = None
     if world > 1 or force_dp:
@@ -799,16 +898,17 @@ def main():
 
     def run_resident(n, start, events=None):
         """the same n optimizer steps with the batch tensors already resident in HBM when the step starts (the bench contract's timed region)"""
+        loss = None
         for i in range(n):
             ids, vis, aco, mask, seg, lab = resident[(start + i) % nb]
-            model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
+            loss = model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
             sch.step()
             if events is not None:
                 events[i + 1].record(torch.cuda.current_stream())
+        return loss
 
     scope = model.stream_scope()          # the whole loop on one private HIP stream (see _MagBertBase.stream_scope)
     scope.__enter__()
-    run(max(2, a.warmup // 2), 0)         # both forms are warmed (each captures its own graph)
     run_resident(a.warmup, 0)
     fence()
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]      # created (and warmed) before the timed region
@@ -817,84 +917,38 @@ def main():
     fence()
     evs[0].record(torch.cuda.current_stream())
     t0 = time.perf_counter()
-    run_resident(a.steps, a.warmup, evs)       # TIMED REGION: exactly K steps, inputs resident in HBM
+    last_loss = run_resident(a.steps, a.warmup, evs)       # TIMED REGION: exactly K steps, inputs resident in HBM
     t_host = time.perf_counter() - t0          # host done enqueueing; the GPU may still be running
     fence()
     dt = time.perf_counter() - t0
     per_step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(len(evs) - 1))
-    # secondary figure: the loop as train_epoch runs it -- every batch comes from HOST memory (one pinned block, gathered across PCIe by the
-    # step's first launch: multimodal_driver.py:359) -- the PCIe-inclusive rate (rounds 1-5 reported THIS as `value`)
-    n2 = max(4, a.steps // 2)
-    fence()
-    t1 = time.perf_counter()
-    run(n2, 0)
-    fence()
-    dt_h2d = (time.perf_counter() - t1) / n2
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, last_loss)
+    n_steps_run = a.warmup + a.steps
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # in-step duration of the two largest kernels of the step -- the per-layer grouped weight-gradient GEMM and the optimizer -- from
-    # HIP events the engine records around them on the stream they run on (profiling events cannot live inside a captured graph:
-    # these steps run the same kernel sequence launch by launch)
+    dt_h2d = host_call_ms = None
     wgrad_in_step_us = adamw_in_step_us = None
-    comm_exposed_ms = None
-    n3 = 0
-    try:
-        import ctypes as C
-        from bert_multimodal_transformer_amd import _lib
-        core = model._core
-        fn = lambda name: getattr(_lib.lib(), "mb_%s_%s" % (core.kind, name))
-        _lib.check(fn("set_profiling")(core.handle, 1))
-        acc, acc_a = [], []
-        for i in range(7):
-            ids, vis, aco, mask, seg, lab = resident[i % nb]
-            model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
-            sch.step()
-            torch.cuda.synchronize()
-            v = C.c_float()
-            _lib.check(fn("profile_wgrad_us")(core.handle, C.byref(v)))
-            acc.append(v.value)
-            if single_call:
-                _lib.check(fn("profile_adamw_us")(core.handle, C.byref(v)))
-                acc_a.append(v.value)
-        _lib.check(fn("set_profiling")(core.handle, 0))
-        wgrad_in_step_us = float(np.median(acc[1:]))
-        adamw_in_step_us = float(np.median(acc_a[1:])) if acc_a else None
-        n3 = 7
-    except Exception as ex:          # MB_GROUP_WGRAD=0 (separate launches): no grouped kernel to time
-        print("note: in-step kernel timing unavailable (%s)" % ex, file=sys.stderr)
-    # host cost of ONE step call with an empty queue (host_enqueue_ms_per_step above is wall time of the enqueue loop: once the host
-    # is a few steps ahead it blocks on the launch queue's depth and the figure approaches the GPU time -- it says nothing about the host)
-    host_call = []
-    for i in range(6):
-        ids, vis, aco, mask, seg, lab = resident[i % nb]
-        torch.cuda.synchronize()
-        th = time.perf_counter()
-        model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
-        sch.step()
-        host_call.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    host_call_ms = float(np.median(host_call[1:])) * 1e3
-    n3 += 6
-    comm_stats = None
-    if dp is not None:
-        if dp_call:          # five more steps with the comm object's timing events on: the compute stream's stalls on the exchange
-            dp.comm.set_timing(True)
-            ex = []
-            for i in range(5):
-                ids, vis, aco, mask, seg, lab = resident[i % nb]
-                model.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt, graph=use_graph)
-                sch.step()
-                ex.append(dp.exposed_ms())
-            dp.comm.set_timing(False)
-            comm_exposed_ms = float(np.median(ex))
-            comm_stats = dp.comm.stats()
-            n3 += 5
-        else:
-            comm_exposed_ms = dp.exposed_ms()
+    comm_exposed_ms = comm_stats = None
+    if a.full:
+        # secondary figure: the loop as train_epoch runs it -- every batch comes from HOST memory (one pinned block, gathered across PCIe by the
+        # step's first launch: multimodal_driver.py:359) -- the PCIe-inclusive rate (rounds 1-5 reported THIS as `value`)
+        n_warm_h2d = max(2, a.warmup // 2)
+        run(n_warm_h2d, 0)                 # this form captures a graph of its own
+        n2 = max(4, a.steps // 2)
+        fence()
+        t1 = time.perf_counter()
+        run(n2, 0)
+        fence()
+        dt_h2d = (time.perf_counter() - t1) / n2
+        n_steps_run += n_warm_h2d + n2
+        wgrad_in_step_us, adamw_in_step_us, host_call_ms, comm_exposed_ms, comm_stats, n3 = full_step_extras(
+            model, opt, sch, resident, nb, use_graph, single_call, dp, dp_call)
+        n_steps_run += n3
     scope.__exit__(None, None, None)
-    loss = float(model.loss_running().item()) / max(1, total_steps + n2 + n3)
+    loss = float(model.loss_running().item()) / max(1, n_steps_run)
     value = world * B * a.steps / dt
 
     out = None
@@ -917,11 +971,13 @@ def main():
                           "h2d": "none inside the timed region (value_with_per_step_h2d: one pinned host block per batch, gathered across PCIe by the step's first launch)",
                           **({"grad_wire_dtype": "bf16" if dp.reducer.wire_dtype == torch.bfloat16 else "fp32"} if dp is not None else {})},
                "mean_loss": round(loss, 4), "host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 3),
-               "host_call_ms_per_step": round(host_call_ms, 3),
                "step_ms_median": q(0.5), "step_ms_p10": q(0.1), "step_ms_p90": q(0.9),
-               "value_with_per_step_h2d": round(world * B / dt_h2d, 2),
                "value_is": "K timed steps with the batch tensors resident in HBM when the step starts (the bench contract); value_with_per_step_h2d = the same "
                            "steps fed from pinned host memory like train_epoch's `.to(DEVICE)` (what rounds 1-5 reported as `value`)"}
+        if host_call_ms is not None:
+            out["host_call_ms_per_step"] = round(host_call_ms, 3)
+        if dt_h2d is not None:
+            out["value_with_per_step_h2d"] = round(world * B / dt_h2d, 2)
         if dp is not None:
             out["rccl_ranks"] = rccl_ranks
             out["devices_visible"] = torch.cuda.device_count()
@@ -937,7 +993,7 @@ def main():
         if gflop:
             out["step_tflops_algorithmic"] = round(value * gflop * 1e-3, 1)
             out["step_mfma_frac"] = round(value * gflop * 1e-3 * 0.984 / (peak * world), 4)
-    if a.roofline and rank == 0:
+    if a.full and a.roofline and rank == 0:
         rl = gemm_roofline(a.dtype, B * L)
         peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
         H_, I_, NL = 768, 3072, 12
@@ -1082,7 +1138,7 @@ def main():
                 out["roofline_hbm"]["instep_replayed" if ik.get("replayed") else "instep"] = rows
         except Exception:
             pass
-    if a.secondary and rank == 0 and world == 1 and dp is None and a.model == "bert" and (B, L, a.dataset, a.dtype) == (48, 50, "mosi", "bf16"):
+    if a.full and a.secondary and rank == 0 and world == 1 and dp is None and a.model == "bert" and (B, L, a.dataset, a.dtype) == (48, 50, "mosi", "bf16"):
         del resident
         torch.cuda.empty_cache()
         out["secondary"] = []
@@ -1092,14 +1148,14 @@ def main():
                                                            cpu_steps=(2 if (kind == "xlnet" and a.cpu_baseline) else 0)))
             except Exception as ex:
                 out["secondary"].append({"metric": "%s %s B=%d L=%d" % (kind, dataset, b2, l2), "error": repr(ex)})
-    if a.epoch and rank == 0 and world == 1 and dp is None and a.model == "bert" and (B, L, a.dataset, a.dtype) == (48, 50, "mosi", "bf16"):
+    if a.full and a.epoch and rank == 0 and world == 1 and dp is None and a.model == "bert" and (B, L, a.dataset, a.dtype) == (48, 50, "mosi", "bf16"):
         try:
             out.update(epoch_mode(a.dtype))
             # the share of train_epoch that is NOT its 26 full-size steps at the timed rate: the ragged step, the first-batch staging, the one host sync
             out["epoch_train_outside_full_steps_ms"] = round(out["epoch_train_ms"] - 26 * 48.0 / out["value_with_per_step_h2d"] * 1e3, 2)
         except Exception as ex:          # noqa: BLE001
             out["epoch_error"] = repr(ex)
-    if a.cpu_baseline and rank == 0 and world == 1:
+    if a.full and a.cpu_baseline and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(B, L, V, A, a.cpu_steps, a.model)
         out["cpu_baseline"].update(cpu_info())
         out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)

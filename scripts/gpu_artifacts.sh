@@ -57,32 +57,32 @@ f=$(find /tmp/p_c5 -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python3 
 # ---- 3. bench.py lines
 cp $O/instep_kernels.json profiles/instep_kernels.json 2>/dev/null
 J='^{"metric'
-(timeout 500 python bench.py 2>&1 | grep "$J") > $O/bench_line.log 2>&1
-(timeout 300 python bench.py --dataset mosei --seq 128 --batch 32 --cpu-baseline 0 --steps 30 --warmup 6 2>&1 | grep "$J") > $O/bench_line_c5.log 2>&1
-(timeout 300 python bench.py --model xlnet --cpu-steps 2 --steps 30 --warmup 6 2>&1 | grep "$J") > $O/bench_line_xlnet.log 2>&1
+(timeout 500 python bench.py --full 2>&1 | grep "$J") > $O/bench_line.log 2>&1
+(timeout 300 python bench.py --full --dataset mosei --seq 128 --batch 32 --cpu-baseline 0 --steps 30 --warmup 6 2>&1 | grep "$J") > $O/bench_line_c5.log 2>&1
+(timeout 300 python bench.py --full --model xlnet --cpu-steps 2 --steps 30 --warmup 6 2>&1 | grep "$J") > $O/bench_line_xlnet.log 2>&1
 # ---- 3b. the data-parallel step on ONE GPU (one-rank RCCL group, MB_DP_FORCE=1) against the single-call step, same box, twice each
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 {
 for rep in 1 2; do
-  echo "== single call (mb_bert_train_step), bench.py"; timeout 300 python bench.py --cpu-baseline 0 --roofline 0 --secondary 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1400
-  echo "== MB_DP_FORCE=1: mb_bert_train_step_dp, one-rank RCCL communicator driven from C, bench.py"; MB_DP_FORCE=1 timeout 300 python bench.py --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1700
+  echo "== single call (mb_bert_train_step), bench.py"; timeout 300 python bench.py --full --cpu-baseline 0 --roofline 0 --secondary 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1400
+  echo "== MB_DP_FORCE=1: mb_bert_train_step_dp, one-rank RCCL communicator driven from C, bench.py"; MB_DP_FORCE=1 timeout 300 python bench.py --full --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1700
 done
-echo "== MB_DP_FORCE=1 MB_DP_ENGINE=0: round-3 structure (passes and exchange driven from Python)"; MB_DP_FORCE=1 MB_DP_ENGINE=0 timeout 300 python bench.py --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1500
-echo "== MB_DP_FORCE=1 MB_DP_GRAD_DTYPE=bf16: the two-GPU wire format forced on one GPU (staging passes)"; MB_DP_FORCE=1 MB_DP_GRAD_DTYPE=bf16 timeout 300 python bench.py --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1500
-echo "== MAG-XLNet single call / MB_DP_FORCE=1"; timeout 300 python bench.py --model xlnet --cpu-baseline 0 --roofline 0 --steps 60 --warmup 10 2>&1 | grep "$J" | cut -c1-1200
-MB_DP_FORCE=1 timeout 300 python bench.py --model xlnet --cpu-baseline 0 --roofline 0 --steps 60 --warmup 10 2>&1 | grep "$J" | cut -c1-1500
+echo "== MB_DP_FORCE=1 MB_DP_ENGINE=0: round-3 structure (passes and exchange driven from Python)"; MB_DP_FORCE=1 MB_DP_ENGINE=0 timeout 300 python bench.py --full --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1500
+echo "== MB_DP_FORCE=1 MB_DP_GRAD_DTYPE=bf16: the two-GPU wire format forced on one GPU (staging passes)"; MB_DP_FORCE=1 MB_DP_GRAD_DTYPE=bf16 timeout 300 python bench.py --full --cpu-baseline 0 --roofline 0 --steps 100 --warmup 20 2>&1 | grep "$J" | cut -c1-1500
+echo "== MAG-XLNet single call / MB_DP_FORCE=1"; timeout 300 python bench.py --full --model xlnet --cpu-baseline 0 --roofline 0 --steps 60 --warmup 10 2>&1 | grep "$J" | cut -c1-1200
+MB_DP_FORCE=1 timeout 300 python bench.py --full --model xlnet --cpu-baseline 0 --roofline 0 --steps 60 --warmup 10 2>&1 | grep "$J" | cut -c1-1500
 for rep in 1 2; do
   echo "== C++ driver: single call"; timeout 120 $SB --graph 1 --h2d 2 --steps 100 --warmup 20
   echo "== C++ driver: --dp 1 (one-rank RCCL communicator)"; timeout 180 $SB --graph 1 --h2d 2 --steps 100 --warmup 20 --dp 1 2>&1 | grep step_bench
   echo "== C++ driver: --dp 1, host cost with an empty queue (5 steps)"; timeout 180 $SB --graph 1 --h2d 2 --steps 5 --warmup 20 --dp 1 2>&1 | grep "ms/step"
 done
 } > $O/dp_force.txt 2>&1
-( cd /tmp && rm -rf /tmp/p_b && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_b -o b -- python $R/bench.py --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 --secondary 0 > /dev/null 2>&1 )
+( cd /tmp && rm -rf /tmp/p_b && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_b -o b -- python $R/bench.py --full --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 --secondary 0 > /dev/null 2>&1 )
 f=$(find /tmp/p_b -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv
-( cd /tmp && rm -rf /tmp/p_x && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_x -o b -- python $R/bench.py --model xlnet --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 > /dev/null 2>&1 )
+( cd /tmp && rm -rf /tmp/p_x && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_x -o b -- python $R/bench.py --full --model xlnet --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 > /dev/null 2>&1 )
 f=$(find /tmp/p_x -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/xlnet_kernel_stats.csv
 # bench.py starting its own ranks (round 5): two ranks sharing this GPU over the callback backend -- the launcher, the rccl_ranks proof and the JSON contract, not a speed
-(MB_DIST_BACKEND=gloo timeout 300 python bench.py --gpus 2 --cpu-baseline 0 --roofline 0 --steps 10 --warmup 3 2>&1 | grep "$J" | cut -c1-1800) > $O/bench_line_gpus2_gloo.log 2>&1
+(MB_DIST_BACKEND=gloo timeout 300 python bench.py --gpus 2 --full --cpu-baseline 0 --roofline 0 --steps 10 --warmup 3 2>&1 | grep "$J" | cut -c1-1800) > $O/bench_line_gpus2_gloo.log 2>&1
 { timeout 60 python bench.py --gpus 2 --cpu-baseline 0 --roofline 0 > $O/.g2.tmp 2>&1; rc=$?; tail -n 2 $O/.g2.tmp; rm -f $O/.g2.tmp; echo "exit code $rc"; } > $O/bench_gpus2_without_devices.log 2>&1
 for f in bench_line bench_line_c5 bench_line_xlnet; do tail -n 1 $O/$f.log | cut -c1-420; done
 cat $O/instep_kernels.txt | head -24
