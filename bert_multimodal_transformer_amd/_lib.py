@@ -52,6 +52,9 @@ PROTOTYPES = {
                                _i, _dk, _vp]),
     "mb_attention_forward": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _dk, _vp]),
     "mb_attention_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp]),
+    "mb_attention_tiled_stats_bytes": (_sz, [_i, _i, _i]),
+    "mb_attention_tiled_forward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp, _vp]),
+    "mb_attention_tiled_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),
     "mb_mag_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mb_mag_forward": (_i, [_i] + [_vp] * 13 + [_f, _dk, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mb_mag_backward": (_i, [_i] + [_vp] * 11 + [_f, _dk] + [_vp] * 14 + [_i, _i, _i, _i, _vp]),

@@ -108,13 +108,28 @@ class _BaseFn(torch.autograd.Function):
         return torch.zeros((), device=core.device), None, None, None, core.inputs_embeds_grad() if ctx.want_emb else None
 
 
+def _seq_limit(config, max_seq_length):
+    """the L limit of a MAG-BERT model built with `max_seq_length` (None: 128, the LDS-resident attention's)"""
+    if max_seq_length is None:
+        return 128
+    n = int(max_seq_length)
+    if n < 1 or n > config.max_position_embeddings:
+        raise ValueError("max_seq_length = %d: must be in [1, max_position_embeddings = %d]" % (n, config.max_position_embeddings))
+    return max(n, 128)
+
+
 class _Core(object):
     """Flat parameter/gradient storage + engine handle shared by the model classes."""
 
     def __init__(self, config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, kind="bert",
-                 injection_index=1):
+                 injection_index=1, max_seq_length=None):
         self.kind = kind                     # "bert" (mb_bert_*) or "xlnet" (mb_xlnet_*)
         self.injection_index = injection_index
+        # MAG-BERT: the longest sequence this instance runs -- None or <= 128 keeps the limit of 128, above it the engine's attention
+        # runs the tiled kernels (up to the position table); MAG-XLNet keeps its own limit in the library
+        self.max_seq_length = None
+        if kind == "bert":
+            self.max_seq_length = _seq_limit(config, max_seq_length)
         if not torch.cuda.is_available():
             raise _lib.MagbertError("MAG-BERT runs on the HIP path only: no ROCm device visible (no CPU fallback)")
         self.lib = _lib.lib()
@@ -216,6 +231,10 @@ class _Core(object):
         # on its own -- piece by piece when the sharded update cut its forward (a full join here would undo that overlap)
         if join:
             self._comm_join()
+        if self.max_seq_length is not None and L > self.max_seq_length:
+            raise _lib.MagbertError("magbert: unsupported shape or alignment: L = %d is above this model's max_seq_length = %d "
+                                    "(construct it with max_seq_length=%d, at most %d)"
+                                    % (L, self.max_seq_length, L, self.config.max_position_embeddings))
         if B > self.max_B or L > self.max_L or self.ws is None:
             # "logically zero, physically stale" gradients are a fact only the OLD engine knows: make them real zeros before it goes
             self.materialize_grads()
@@ -1010,11 +1029,14 @@ class MAG_BertModel(_MagBertBase):
     (not differentiable; the trainable surface is MAG_BertForSequenceClassification, which is what the driver uses)."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None, _core=None):
+                 compute_dtype=torch.float32, device=None, _core=None, max_seq_length=None):
+        """max_seq_length: the longest sequence this instance will run (None or <= 128: 128; at most
+        config.max_position_embeddings, ValueError above)."""
         super().__init__()
         self.config = config
         own = _core is None
-        self._core = _core or _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device)
+        self._core = _core or _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device,
+                                    max_seq_length=max_seq_length)
         _attach_parameters(self, self._core, prefix_filter="bert.", strip="bert.")
         if own:
             self.init_weights()
@@ -1066,11 +1088,12 @@ class MAG_BertForSequenceClassification(_FusedStep, _MagBertBase):
     """bert.py:240-324."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None):
+                 compute_dtype=torch.float32, device=None, max_seq_length=None):
+        """max_seq_length: as MAG_BertModel's."""
         super().__init__()
         self.config = config
         self.num_labels = config.num_labels
-        self._core = _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device)
+        self._core = _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, max_seq_length=max_seq_length)
         self.bert = MAG_BertModel(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, _core=self._core)
         self.dropout = nn.Dropout(config.hidden_dropout_prob)        # bert.py:246 (p lives in the engine config)
         _attach_parameters(self, self._core, prefix_filter="classifier.")

@@ -1,4 +1,5 @@
-// LDS-resident fused self-attention for the BERT encoder, forward and backward (dh = 64, L <= 128).
+// LDS-resident fused self-attention for the BERT encoder, forward and backward (dh = 64, L <= 128; longer sequences:
+// attention_tiled.hip, dispatched from attention_forward / attention_backward below).
 //
 // Replaces BertSelfAttention's score bmm + scale + mask add + softmax + dropout + context bmm + permutes
 // (transformers 3.0.2, reached from /root/reference/bert.py:221-229):
@@ -469,8 +470,9 @@ int attention_backward_free_slots(int dtype, int L, int nblk, int cus) {
 }
 
 int attention_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh, DropKey drop,
-                      hipStream_t st, float* probs, const float* head_scale) {
-    if (L < 1 || L > 128) return MB_ERR_SHAPE;
+                      hipStream_t st, float* probs, const float* head_scale, float* stats) {
+    if (L > 128) return attention_tiled_forward(dtype, qkv, mask, ctx, stats, B, L, nh, drop, st, probs, head_scale);
+    if (L < 1) return MB_ERR_SHAPE;
     const int LP = (L + 31) / 32 * 32;
     if (dtype == DT_BF16) {
         switch (LP) {
@@ -491,9 +493,11 @@ int attention_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx
 }
 
 int attention_backward(int dtype, const void* qkv, const int64_t* mask, const void* ctx, const void* dctx, void* dqkv,
-                       float* dbias, int B, int L, int nh, DropKey drop, hipStream_t st, const float* head_scale, GradAcc acc, const AdamRide* ride) {
-    (void)ctx;   // D_i is recomputed as sum_j dP_ij P_ij, the forward output is not needed
-    if (L < 1 || L > 128) return MB_ERR_SHAPE;
+                       float* dbias, int B, int L, int nh, DropKey drop, hipStream_t st, const float* head_scale, GradAcc acc, const AdamRide* ride,
+                       float* stats) {
+    if (L > 128) return attention_tiled_backward(dtype, qkv, mask, ctx, dctx, stats, dqkv, dbias, B, L, nh, drop, st, head_scale, acc, ride);
+    // (L <= 128: D_i is recomputed as sum_j dP_ij P_ij, the forward output is not needed)
+    if (L < 1) return MB_ERR_SHAPE;
     const int LP = (L + 31) / 32 * 32;
     if (dtype == DT_BF16) {
         switch (LP) {

@@ -18,7 +18,7 @@
 
 // ================================================================================================ engine
 struct LayerOff { size_t wqkv, wo, w1, w2, bqkv, bo, ln1w, ln1b, b1, b2, ln2w, ln2b; };
-struct LayerWs { size_t qkv, ctx, s1, st1, y1, u, g, s2, st2; };
+struct LayerWs { size_t qkv, ctx, s1, st1, y1, u, g, s2, st2, stats; };     // stats: tiled attention's row statistics (max_seq > 128 only)
 
 struct mb_bert_engine : StepMixin {
     mb_bert_config c;
@@ -104,6 +104,7 @@ struct mb_bert_engine : StepMixin {
         return c.dtype == DT_BF16 ? (const void*)(SH + off * 2) : (const void*)(P + off);
     }
     DropKey key(uint32_t site, float p) const { return step_key(ws, training != 0, seed, step, site, p); }
+    float* attn_stats(const LayerWs& w) const { return c.max_seq > 128 ? (float*)(ws + w.stats) : nullptr; }
 };
 
 static void build_layout(mb_bert_engine* e) {
@@ -182,6 +183,9 @@ static void build_layout(mb_bert_engine* e) {
         x.qkv = w.take(T * 3 * H * es); x.ctx = w.take(T * H * es); x.s1 = w.take(T * H * es); x.st1 = w.take(2 * T * 4);
         x.y1 = w.take(T * H * es); x.u = w.take(T * I * es); x.g = w.take(T * I * es); x.s2 = w.take(T * H * es);
         x.st2 = w.take(2 * T * 4);
+        // L > 128 runs the tiled attention kernels, whose forward leaves row statistics for the backward (engines built for
+        // max_seq <= 128 carve exactly what they always did)
+        x.stats = c.max_seq > 128 ? w.take(tiled_stats_floats(c.max_batch, c.max_seq, c.num_heads) * 4) : 0;
     }
     e->ws_head_z = w.take((size_t)c.max_batch * H * 4);
     e->ws_head_pooled = w.take((size_t)c.max_batch * H * 4);
@@ -332,6 +336,7 @@ int mb_embed_backward(int dtype, const void* dout, const int64_t* ids, const int
 }
 int mb_attention_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
                          const mb_dropkey* drop, void* stream) {
+    if (L > 128) return MB_ERR_SHAPE;      // (the LDS-resident pair; longer sequences: mb_attention_tiled_*)
     return attention_forward(dtype, qkv, mask, ctx, B, L, nh, dk(drop), (hipStream_t)stream);
 }
 int mb_attention_backward(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L,
@@ -345,8 +350,21 @@ int mb_attention_backward(int dtype, const void* qkv, const int64_t* mask, const
         if (trace_on && (hipMalloc(&trace_dbias, (size_t)3 * 64 * 64 * sizeof(float)) != hipSuccess ||
                          hipMemset(trace_dbias, 0, (size_t)3 * 64 * 64 * sizeof(float)) != hipSuccess)) trace_dbias = nullptr;
     }
+    if (L > 128) return MB_ERR_SHAPE;
     return attention_backward(dtype, qkv, mask, nullptr, dctx, dqkv, (trace_on && nh <= 64) ? trace_dbias : nullptr, B, L, nh, dk(drop),
                               (hipStream_t)stream);
+}
+size_t mb_attention_tiled_stats_bytes(int B, int L, int nh) {
+    return (B < 1 || L < 1 || nh < 1) ? 0 : tiled_stats_floats(B, L, nh) * sizeof(float);
+}
+int mb_attention_tiled_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, float* stats, int B, int L, int nh,
+                               const mb_dropkey* drop, const float* head_scale, float* probs, void* stream) {
+    return attention_tiled_forward(dtype, qkv, mask, ctx, stats, B, L, nh, dk(drop), (hipStream_t)stream, probs, head_scale);
+}
+int mb_attention_tiled_backward(int dtype, const void* qkv, const int64_t* mask, const void* ctx, const void* dctx, float* stats,
+                                void* dqkv, float* dbias, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                                void* stream) {
+    return attention_tiled_backward(dtype, qkv, mask, ctx, dctx, stats, dqkv, dbias, B, L, nh, dk(drop), (hipStream_t)stream, head_scale);
 }
 
 size_t mb_mag_workspace_bytes(int dtype, int T, int H, int V, int A) {
@@ -394,7 +412,8 @@ int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n
 int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (!cfg || !out) return MB_ERR_ARG;
     if (cfg->hidden_size != 768 || cfg->num_heads * 64 != cfg->hidden_size) return MB_ERR_SHAPE;
-    if (cfg->intermediate_size % 128 || cfg->max_seq < 1 || cfg->max_seq > 128 || cfg->max_batch < 1) return MB_ERR_SHAPE;
+    // max_seq > 128: the tiled attention kernels (up to 512 = BERT's position table)
+    if (cfg->intermediate_size % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1) return MB_ERR_SHAPE;
     if (cfg->max_seq > cfg->max_position || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
     mb_bert_engine* e = new mb_bert_engine();
@@ -525,7 +544,7 @@ static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const
         CK(attention_forward(dt, ws + w.qkv, attention_mask, ws + w.ctx, B, L, nh,
                              e->key(SITE_LAYER0 + 4 * l + 0, c.attn_dropout), st,
                              e->attn_out ? e->attn_out + (size_t)l * B * nh * L * L : nullptr,
-                             e->head_mask ? e->head_mask + (size_t)l * nh : nullptr));
+                             e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, e->attn_stats(w)));
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, T, H, H, ws + w.ctx, H, e->W(o.wo), H, ws + w.s1, H, nullptr, nullptr,
                 P + o.bo, x, H, e->key(SITE_LAYER0 + 4 * l + 1, c.hidden_dropout), 1, 0, st));
         // (the two LayerNorm launches of a layer touch the weights of the GEMMs behind them: W1 | W2, then the next layer's Wqkv | Wo)
@@ -707,7 +726,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             // (riders: the launch's empty block slots -- L <= 64: 448 of 1024 next to a latency-bound kernel; L = 128: the 128 CUs its second
             //  round leaves idle -- carry a piece of the optimizer update; MB_ADAMW_RIDE_ATTN=0 turns them off)
             AdamRide ra = {};
-            if (e->ride_attn && inl && e->ride_m) {
+            if (e->ride_attn && inl && e->ride_m && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
                 int free_slots = attention_backward_free_slots(dt, L, B * nh, e->cu_count());
                 if (e->ride_attn_blocks > 0) free_slots = e->ride_attn_blocks;
                 const int blocks = std::min(free_slots, 2 * e->cu_count()) / 8 * 8;
@@ -726,7 +745,8 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             }
             CK(attention_backward(dt, ws + w.qkv, e->mask, ws + w.ctx, ws + e->ws_dctx, dqkv, G + o.bqkv, B, L, nh,
                                   e->key(SITE_LAYER0 + 4 * l + 0, c.attn_dropout), st,
-                                  e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, ra.blocks ? &ra : nullptr));
+                                  e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, ra.blocks ? &ra : nullptr,
+                                  e->attn_stats(w)));
             // (experiment) the update inside the launch: the tile of the gradient becomes the new parameters -- so every reader of the
             // OLD weights of this layer (the qkv dgrad below) goes first
             const bool fuse = inl && e->fuse_m && e->fuse_v && e->ow_pass && e->group_wgrad == 128;

@@ -196,13 +196,26 @@ int mag_gate_backward(int dtype, const void* dout, const void* e, const void* Ze
 // ctx: [B*L][H].  softmax(QK^T/sqrt(dh) + (1-mask)*-10000) -> dropout -> . V   (dh = 64, L <= 128)
 // probs (fp32 [B][nh][L][L], may be null): the attention probabilities after dropout and head mask (output_attentions)
 // head_scale (fp32 [nh], may be null): head_mask of this layer -- the dropped probabilities of head h are multiplied by it
+// stats (fp32, tiled_stats_floats(B, L, nh), may be null for L <= 128): the row statistics the forward leaves for the backward
+// L <= 128: the LDS-resident kernels (attention.hip); 128 < L <= 512: the tiled ones (attention_tiled.hip), which need stats and
+// ctx (the backward's D_i = dO_i . ctx_i) and take no riders
 int attention_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
-                      DropKey drop, hipStream_t st, float* probs = nullptr, const float* head_scale = nullptr);
+                      DropKey drop, hipStream_t st, float* probs = nullptr, const float* head_scale = nullptr,
+                      float* stats = nullptr);
 // dbias (fp32 [3H], may be null): += column sums of dqkv (bias grads of the fused QKV Linear)
 int attention_backward(int dtype, const void* qkv, const int64_t* mask, const void* ctx, const void* dctx,
                        void* dqkv, float* dbias, int B, int L, int nh, DropKey drop, hipStream_t st,
                        const float* head_scale = nullptr, GradAcc acc = {},
-                       const struct AdamRide* ride = nullptr);      // bf16: AdamW riders behind the (batch, head) workgroups (AdamRide below)
+                       const struct AdamRide* ride = nullptr,      // bf16: AdamW riders behind the (batch, head) workgroups (AdamRide below)
+                       float* stats = nullptr);
+// the tiled kernels at any 1 <= L <= 512 (attention_tiled.hip): stats = three fp32 planes of B*nh*L rows (m | 1/l | D); the backward
+// returns MB_ERR_MODE when handed riders, MB_ERR_SHAPE when dropout is on and B*nh*L*L does not fit the uint32 mask index
+size_t tiled_stats_floats(int B, int L, int nh);
+int attention_tiled_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, float* stats, int B, int L, int nh,
+                            DropKey drop, hipStream_t st, float* probs = nullptr, const float* head_scale = nullptr);
+int attention_tiled_backward(int dtype, const void* qkv, const int64_t* mask, const void* ctx, const void* dctx, float* stats,
+                             void* dqkv, float* dbias, int B, int L, int nh, DropKey drop, hipStream_t st,
+                             const float* head_scale = nullptr, GradAcc acc = {}, const struct AdamRide* ride = nullptr);
 int attention_backward_free_slots(int dtype, int L, int nblk, int cus);      // workgroups that fit the last round of that launch
 int attention_trace_fetch(unsigned long long* host_out, int max_blocks);     // MB_ATTN_TRACE=1: stamps of the last attention_backward
 

@@ -369,10 +369,10 @@ def prep_for_training(num_train_optimization_steps: int):
         if args.pretrained:
             model = MAG_BertForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt)
+                compute_dtype=dt, max_seq_length=args.max_seq_length)
         else:       # offline: fresh init by the reference's init law
             model = MAG_BertForSequenceClassification(BertConfig(num_labels=1), multimodal_config, visual_dim=V,
-                                                      acoustic_dim=A, compute_dtype=dt)
+                                                      acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     elif args.model == "xlnet-base-cased":
         from .xlnet import MAG_XLNetForSequenceClassification, XLNetConfig
         if args.pretrained:

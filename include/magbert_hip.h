@@ -88,11 +88,23 @@ int mb_embed_backward(int dtype, const void* dout, const int64_t* ids, const int
                       int H, int pad_id, const mb_dropkey* drop, void* stream);
 
 /* BertSelfAttention core (bert.py:221-229): ctx = dropout(softmax(QK^T/8 + (1-mask)*-1e4)) V.
- * qkv [T][3H] token-major, mask int64 [B][L], ctx/dctx [T][H], dqkv [T][3H].  L <= 128, head dim 64. */
+ * qkv [T][3H] token-major, mask int64 [B][L], ctx/dctx [T][H], dqkv [T][3H].  L <= 128 (MB_ERR_SHAPE above), head dim 64. */
 int mb_attention_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
                          const mb_dropkey* drop, void* stream);
 int mb_attention_backward(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L,
                           int nh, const mb_dropkey* drop, void* stream);
+/* The tiled kernels the engines run for 128 < L <= 512, usable at any 1 <= L <= 512 (same arithmetic; 64-row blocks streamed through
+ * LDS instead of a whole sequence per head).  stats: caller scratch of mb_attention_tiled_stats_bytes(B, L, nh) -- the forward leaves
+ * the row statistics of the backward in it (the backward also uses it as scratch).  head_scale fp32 [nh] or NULL (head_mask);
+ * probs fp32 [B][nh][L][L] or NULL: the probabilities after dropout, times head_scale (output_attentions).  The backward also
+ * needs the forward's ctx; dbias fp32 [3H] or NULL: += the column sums of dqkv.  MB_ERR_SHAPE when dropout is on and
+ * B*nh*L*L >= 2^32 (the mask index is 32-bit). */
+size_t mb_attention_tiled_stats_bytes(int B, int L, int nh);
+int mb_attention_tiled_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, float* stats, int B, int L, int nh,
+                               const mb_dropkey* drop, const float* head_scale, float* probs, void* stream);
+int mb_attention_tiled_backward(int dtype, const void* qkv, const int64_t* mask, const void* ctx, const void* dctx, float* stats,
+                                void* dqkv, float* dbias, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                                void* stream);
 
 /* Multimodal Adaptation Gate, MAG.forward (modeling.py:25-51) and its adjoint, for T tokens.
  * Parameters in the REFERENCE layout: W_hv [H][V+H], W_ha [H][A+H], W_v [H][V], W_a [H][A], biases [H], LayerNorm [H].
@@ -127,7 +139,8 @@ typedef struct {
     float layer_norm_eps, mag_layer_norm_eps, beta_shift;
     float hidden_dropout, attn_dropout, mag_dropout;
     int dtype;       /* MB_DT_* */
-    int max_batch, max_seq;
+    int max_batch, max_seq;      /* max_seq <= min(512, max_position); above 128 the attention runs the tiled kernels and the
+                                    workspace holds their row statistics (engines of max_seq <= 128 carve exactly what they did) */
 } mb_bert_config;
 
 typedef struct mb_bert_engine mb_bert_engine;

@@ -1,0 +1,310 @@
+"""GPU: MAG-BERT on sequences longer than 128 tokens (the tiled attention kernels, csrc/attention_tiled.hip).
+
+Op level: the tiled pair against fp64 torch (bounds of test_ops_gpu.test_attention_forward_backward) and against the LDS-resident
+pair at L <= 128.  Model level: the live CPU oracle, whose attention has no length-specific code."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from bert_multimodal_transformer_amd import AdamW, BertConfig, MAG_BertForSequenceClassification, MultimodalConfig, _lib, rng
+from bert_multimodal_transformer_amd import get_linear_schedule_with_warmup
+from oracle import mag_bert_ref as R, weights
+from test_model_gpu import DEV, LOOSE_BF16, _grad_report, _Replay, build, oracle, tb
+from test_ops_gpu import _attn_ref, close, rnd, stream
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DTS = [(_lib.DT_F32, torch.float32), (_lib.DT_BF16, torch.bfloat16)]
+
+
+def long_batch(B, L, V=47, seed=5):
+    """synthetic_bert_batch with row 0 at full length L (keys beyond 128 live) and row 1 nearly all padding"""
+    b = weights.synthetic_bert_batch(B, L, V, 74, seed=seed)
+    for r, k in ((0, L - 2), (1, 1)):
+        if r >= B:
+            continue
+        b["input_ids"][r] = 0
+        b["input_ids"][r, 0] = 101
+        b["input_ids"][r, 1:1 + k] = 2000 + (torch.arange(k).numpy() * 7919) % 20000
+        b["input_ids"][r, 1 + k] = 102
+        b["input_mask"][r] = 0
+        b["input_mask"][r, :k + 2] = 1
+        b["visual"][r, 1 + k:] = 0
+        b["acoustic"][r, 1 + k:] = 0
+    return b
+
+
+def make(cdt=torch.float32, layers=2, max_seq_length=512, hidden_p=0.0, attn_p=0.0, p_mag=0.0):
+    cfg = BertConfig(num_hidden_layers=layers, num_labels=1, hidden_dropout_prob=hidden_p, attention_probs_dropout_prob=attn_p)
+    m = MAG_BertForSequenceClassification(cfg, MultimodalConfig(1.0, p_mag), visual_dim=47, acoustic_dim=74, compute_dtype=cdt,
+                                          max_seq_length=max_seq_length)
+    m.load_state_dict({n: torch.from_numpy(weights.make_param(n, tuple(p.shape))) for n, p in m.named_parameters()})
+    return m
+
+
+def eval_logits(m, b):
+    ids, vis, aco, mask, seg, _ = tb(b, DEV)
+    with torch.no_grad():
+        return m(ids, vis, aco, token_type_ids=seg, attention_mask=mask)[0].float().cpu()
+
+
+def oracle_logits(o, b):
+    i2, v2, a2, m2, s2, _ = tb(b)
+    with torch.no_grad():
+        return o(i2, v2, a2, m2, s2)[0]
+
+
+# ------------------------------------------------------------------------------------------------------------ op level
+def _tiled(dt, tdt, qd, md, dctx_d, B, S, nh, key, hs=None, probs=False, dbias=False):
+    L = _lib.lib()
+    H = nh * 64
+    stats = torch.zeros(L.mb_attention_tiled_stats_bytes(B, S, nh) // 4, dtype=torch.float32, device=DEV)
+    out = torch.zeros(B * S, H, dtype=tdt, device=DEV)
+    pr = torch.zeros(B, nh, S, S, dtype=torch.float32, device=DEV) if probs else None
+    kp = C.byref(key) if key is not None else None
+    _lib.check(L.mb_attention_tiled_forward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(out), _lib.ptr(stats), B, S, nh, kp,
+                                            _lib.ptr(hs), _lib.ptr(pr), stream()))
+    dq = torch.zeros(B * S, 3 * H, dtype=tdt, device=DEV)
+    db = torch.zeros(3 * H, dtype=torch.float32, device=DEV) if dbias else None
+    _lib.check(L.mb_attention_tiled_backward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(out), _lib.ptr(dctx_d), _lib.ptr(stats),
+                                             _lib.ptr(dq), _lib.ptr(db), B, S, nh, kp, _lib.ptr(hs), stream()))
+    torch.cuda.synchronize()
+    return out, dq, pr, db
+
+
+@pytest.mark.parametrize("dt,tdt", DTS)
+@pytest.mark.parametrize("S", [64, 128, 129, 200, 256, 384, 512])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_tiled_attention_vs_fp64(dt, tdt, S, p):
+    B, nh = 2, 12
+    H = nh * 64
+    qkv = rnd((B * S, 3 * H), 1, tdt, 2.0).requires_grad_(True)
+    mask = torch.ones(B, S, dtype=torch.long)
+    mask[0, S - 7:] = 0
+    mask[1, 3:] = 0                                                      # nearly everything padded
+    dctx = rnd((B * S, H), 2, tdt)
+    hs = torch.linspace(0.5, 1.5, nh, dtype=torch.float32)
+    hs[3] = 0.0
+    key, pmask = None, None
+    if p > 0:
+        key = _lib.make_dropkey(7, 5, 16, p)
+        pmask = torch.from_numpy(rng.keep_mult(B * nh * S * S, rng.make_key(7, 5, 16, p))).view(B, nh, S, S).double()
+    pm = (pmask if pmask is not None else torch.ones(B, nh, S, S, dtype=torch.float64)) * hs.double()[None, :, None, None]
+    ctx = _attn_ref(qkv.double(), mask, B, S, nh, pm)
+    ctx.backward(dctx.double())
+    q, k, _ = qkv.detach().double().view(B, S, 3, nh, 64).permute(2, 0, 3, 1, 4)
+    pref = torch.softmax(q @ k.transpose(-1, -2) / 8.0 + (1.0 - mask[:, None, None, :].double()) * -10000.0, -1) * pm
+    qd, md, dcd, hsd = qkv.detach().to(DEV, tdt), mask.to(DEV), dctx.to(DEV, tdt), hs.to(DEV)
+    out, dq, pr, db = _tiled(dt, tdt, qd, md, dcd, B, S, nh, key, hsd, probs=True, dbias=True)
+    close(out.float(), ctx.detach().float(), dt, "tiled fwd", 2.0)
+    close(pr, pref.float(), dt, "tiled probs", 2.0)
+    close(dq.float(), qkv.grad.float(), dt, "tiled bwd", 3.0)
+    close(db, qkv.grad.double().sum(0).float(), dt, "tiled dbias", 3.0)
+    # without dbias: every dQ / dK / dV element has one writer -> bit-identical reruns
+    _, dq1, _, _ = _tiled(dt, tdt, qd, md, dcd, B, S, nh, key, hsd)
+    _, dq2, _, _ = _tiled(dt, tdt, qd, md, dcd, B, S, nh, key, hsd)
+    assert torch.equal(dq1, dq2)
+    if S <= 128:            # the LDS-resident pair at the same shape (no head_scale in its op-level ABI)
+        L = _lib.lib()
+        kp = C.byref(key) if key is not None else None
+        ref_out = torch.zeros(B * S, H, dtype=tdt, device=DEV)
+        _lib.check(L.mb_attention_forward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(ref_out), B, S, nh, kp, stream()))
+        ref_dq = torch.zeros(B * S, 3 * H, dtype=tdt, device=DEV)
+        _lib.check(L.mb_attention_backward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(dcd), _lib.ptr(ref_dq), B, S, nh, kp, stream()))
+        t_out, t_dq, _, _ = _tiled(dt, tdt, qd, md, dcd, B, S, nh, key)
+        close(t_out.float(), ref_out.float().cpu(), dt, "tiled vs resident fwd", 2.0)
+        close(t_dq.float(), ref_dq.float().cpu(), dt, "tiled vs resident bwd", 3.0)
+
+
+# ------------------------------------------------------------------------------------------------------------ model level
+@pytest.mark.parametrize("B,L,layers,cdt,tol", [(2, 256, 2, torch.float32, 1e-3), (3, 300, 2, torch.float32, 1e-3),
+                                                (2, 512, 2, torch.float32, 1e-3), (2, 256, 12, torch.float32, 1e-3),
+                                                (2, 512, 12, torch.float32, 1e-3), (2, 512, 12, torch.bfloat16, 2e-2)])
+def test_eval_logits_vs_oracle(B, L, layers, cdt, tol):
+    m = make(cdt, layers).eval()
+    o = oracle(layers=layers, p_mag=0.0).eval()
+    b = long_batch(B, L)
+    err = float((eval_logits(m, b) - oracle_logits(o, b)).abs().max())
+    print("B=%d L=%d layers=%d %s max|err| %.3e" % (B, L, layers, cdt, err))
+    assert err <= tol
+
+
+@pytest.mark.parametrize("cdt,tol_logit,tol_grad,layers,B,L", [
+    (torch.float32, 1e-3, 5e-3, 2, 2, 256),
+    (torch.bfloat16, 1e-2, 3e-2, 2, 2, 256),
+    (torch.bfloat16, 2e-2, 3e-2, 12, 8, 512),
+])
+def test_train_mode_dropout_mask_replay_long(cdt, tol_logit, tol_grad, layers, B, L):
+    V, nh, H = 47, 12, 768
+    torch.manual_seed(99)
+    m = make(cdt, layers, hidden_p=0.1, attn_p=0.1, p_mag=0.5).train()
+    o = oracle(V, layers).train()
+    core = m._core
+    b = long_batch(B, L, seed=41)
+    ids, vis, aco, mask, seg, lab = tb(b, DEV)
+    logits = m(ids, vis, aco, token_type_ids=seg, attention_mask=mask, labels=None)[0]
+    torch.nn.MSELoss()(logits.view(-1), lab.view(-1)).backward()
+    seed, step = core.seed, core.step
+    mult = lambda site, p, n: torch.from_numpy(rng.keep_mult(n, rng.make_key(seed, step, site, p)))
+    T = B * L
+    o.bert.embeddings.dropout = _Replay(mult(rng.SITE_EMB, 0.1, T * H))
+    o.bert.MAG.dropout = _Replay(mult(rng.SITE_MAG, 0.5, T * H))
+    o.dropout = _Replay(mult(rng.SITE_HEAD, 0.1, B * H))
+    for l, lyr in enumerate(o.bert.encoder.layer):
+        lyr.attention.self.dropout = _Replay(mult(rng.SITE_LAYER0 + 4 * l + 0, 0.1, B * nh * L * L))
+        lyr.attention.output.dropout = _Replay(mult(rng.SITE_LAYER0 + 4 * l + 1, 0.1, T * H))
+        lyr.output.dropout = _Replay(mult(rng.SITE_LAYER0 + 4 * l + 2, 0.1, T * H))
+    i2, v2, a2, m2, s2, l2 = tb(b)
+    lo = o(i2, v2, a2, m2, s2)[0]
+    torch.nn.functional.mse_loss(lo.view(-1), l2.view(-1)).backward()
+    torch.cuda.synchronize()
+    err = float((logits.detach().cpu() - lo.detach()).abs().max())
+    print("train-mode logits max|err|:", err)
+    assert err <= tol_logit
+    _grad_report(m, o, tol_grad, frobenius=(cdt == torch.bfloat16), loose=LOOSE_BF16 + ("classifier.bias",), tol_loose=1e-1, show=4)
+
+
+def _steps(cdt, graph, L, B=3, nsteps=3, layers=2):
+    from bert_multimodal_transformer_amd.multimodal_driver import optimizer_grouped_parameters
+    torch.manual_seed(77)
+    m = make(cdt, layers, hidden_p=0.0, attn_p=0.0).train()
+    opt = AdamW(optimizer_grouped_parameters(m), lr=1e-4)
+    sch = get_linear_schedule_with_warmup(opt, 0, 10)
+    b = long_batch(B, L, seed=60)
+    gb = tb(b, DEV)
+    losses = []
+    for _ in range(nsteps):
+        losses.append(float(m.train_step(*gb, optimizer=opt, graph=graph)))     # graph False: kernels launched one by one
+        sch.step()
+    torch.cuda.synchronize()
+    return m, losses, b
+
+
+def test_graph_step_tracks_oracle_trajectory_fp32():
+    """three AdamW steps through the single-call (replayed graph) step at L = 200 vs the oracle with the same optimizer"""
+    from oracle import optim_ref
+    m, losses, b = _steps(torch.float32, True, 200)
+    assert m._core.graph_stats()[1] >= 2
+    o = R.set_dropout(oracle(layers=2, p_mag=0.0), 0.0, 0.0, 0.0).train()
+    i2, v2, a2, m2, s2, l2 = tb(b)
+    oo = optim_ref.AdamW(optim_ref.grouped_parameters(o), lr=1e-4)
+    sch = optim_ref.get_linear_schedule_with_warmup(oo, 0, 10)
+    ref = []
+    for _ in range(3):
+        loss = torch.nn.functional.mse_loss(o(i2, v2, a2, m2, s2)[0].view(-1), l2.view(-1))
+        ref.append(float(loss.detach()))
+        loss.backward()
+        oo.step()
+        oo.zero_grad()
+        sch.step()
+    print("losses", losses, "oracle", ref)
+    for a, r in zip(losses, ref):
+        assert abs(a - r) <= 1e-3 * max(1.0, abs(r))
+    m.eval()
+    o.eval()
+    assert float((eval_logits(m, b) - oracle_logits(o, b)).abs().max()) <= 2e-3
+
+
+def test_graph_step_equals_launch_by_launch(monkeypatch):
+    """deterministic mode (as test_model_gpu's graph-vs-eager test in bf16): same bits; the loss scalar is summed by fp32 atomics"""
+    monkeypatch.setenv("MB_DETERMINISTIC", "1")
+    g, lg, _ = _steps(torch.bfloat16, True, 256)
+    e, le, _ = _steps(torch.bfloat16, False, 256)
+    assert g._core.graph_stats()[1] >= 2 and e._core.graph_stats() == (0, 0)
+    for x, y in ((g.flat_params, e.flat_params), (g._core._adam_m, e._core._adam_m), (g._core._adam_v, e._core._adam_v),
+                 (g._core.shadow, e._core.shadow)):
+        assert torch.equal(x, y)
+    assert max(abs(a - b) for a, b in zip(lg, le)) <= 2e-3
+
+
+def test_optional_arguments_long():
+    L, B, layers = 256, 2, 2
+    m = make(torch.float32, layers).eval()
+    o = oracle(layers=layers, p_mag=0.0).eval()
+    b = long_batch(B, L)
+    ids, vis, aco, mask, seg, _ = tb(b, DEV)
+    i2, v2, a2, m2, s2, _ = tb(b)
+    with torch.no_grad():
+        got = m(ids, vis, aco, token_type_ids=seg, attention_mask=mask, output_attentions=True)
+        o(i2, v2, a2, m2, s2)
+    att = got[-1]
+    assert len(att) == layers and tuple(att[0].shape) == (B, 12, L, L)
+    for a, lyr in zip(att, o.bert.encoder.layer):
+        assert float((a.cpu() - lyr.attention.self.last_probs).abs().max()) <= 1e-4
+    hm = torch.ones(layers, 12)
+    hm[0, 2] = 0.0
+    hm[1, 5] = 0.5
+    pos = torch.arange(L).flip(0)[None].expand(B, L).contiguous()
+    with torch.no_grad():
+        for kw, okw in (({"head_mask": hm.to(DEV)}, {"head_mask": hm}), ({"position_ids": pos.to(DEV)}, {"position_ids": pos})):
+            g = m(ids, vis, aco, token_type_ids=seg, attention_mask=mask, **kw)[0].float().cpu()
+            r = o(i2, v2, a2, m2, s2, **okw)[0]
+            assert float((g - r).abs().max()) <= 1e-3, kw.keys()
+
+
+def test_determinism_and_riders_long(monkeypatch):
+    monkeypatch.setenv("MB_DETERMINISTIC", "1")
+    runs = []
+    for ride in ("0", "1", "1"):
+        monkeypatch.setenv("MB_ADAMW_RIDE", ride)
+        monkeypatch.setenv("MB_ADAMW_RIDE_ATTN_BLOCKS", "64")        # (an override the L > 128 path must ignore)
+        m, losses, b = _steps(torch.bfloat16, True, 256, B=4)
+        m.eval()
+        runs.append((m.flat_params.clone(), m._core._adam_m.clone(), m._core._adam_v.clone(), m._core.shadow.clone(), eval_logits(m, b)))
+        del m
+    for x, y in zip(runs[1], runs[2]):
+        assert torch.equal(x, y)             # deterministic mode: two runs, same bits
+    for x, y in zip(runs[0], runs[1]):
+        assert torch.equal(x, y)             # riders on / off: same bits
+
+
+def test_limits():
+    m = make(torch.float32, 1, max_seq_length=256).eval()
+    with torch.no_grad():
+        assert torch.isfinite(eval_logits(m, long_batch(2, 256))).all()
+    with pytest.raises(_lib.MagbertError) as ei:
+        eval_logits(m, long_batch(2, 257))
+    assert "unsupported shape" in str(ei.value) and "max_seq_length" in str(ei.value)
+    with pytest.raises(ValueError):
+        make(torch.float32, 1, max_seq_length=513)
+    # the L <= 128 path is untouched: a model declared for 512 gives the default model's bits at L = 50
+    b = long_batch(3, 50)
+    a = eval_logits(make(torch.bfloat16, 2, max_seq_length=512).eval(), b)
+    d = eval_logits(make(torch.bfloat16, 2, max_seq_length=None).eval(), b)
+    assert torch.equal(a, d)
+
+
+def test_from_pretrained_forwards_max_seq_length(tmp_path):
+    m = make(torch.float32, 1)
+    torch.save({k: v.cpu() for k, v in m.state_dict().items() if k.startswith("bert.")}, tmp_path / "pytorch_model.bin")
+    cfg = BertConfig(num_hidden_layers=1, num_labels=1)
+    p = MAG_BertForSequenceClassification.from_pretrained(str(tmp_path), config=cfg, multimodal_config=MultimodalConfig(1.0, 0.0),
+                                                          visual_dim=47, acoustic_dim=74, max_seq_length=300)
+    assert p._core.max_seq_length == 300
+    with torch.no_grad():
+        assert torch.isfinite(eval_logits(p.eval(), long_batch(2, 300))).all()
+
+
+def test_eval_at_the_drivers_dev_batch():
+    """B = 128, L = 512, bf16, 12 layers: the first four rows against the oracle run on those four samples"""
+    B, L = 128, 512
+    m = make(torch.bfloat16, 12).eval()
+    b = long_batch(B, L, seed=17)
+    got = eval_logits(m, b)
+    assert torch.isfinite(got).all()
+    b4 = {k: v[:4] for k, v in b.items()}
+    ref = oracle_logits(oracle(layers=12, p_mag=0.0).eval(), b4)
+    assert float((got[:4] - ref).abs().max()) <= 2e-2
+
+
+def test_driver_runs_at_256():
+    env = dict(os.environ)
+    r = subprocess.run([sys.executable, "-m", "bert_multimodal_transformer_amd.multimodal_driver", "--synthetic", "96",
+                        "--max_seq_length", "256", "--n_epochs", "1", "--train_batch_size", "16"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

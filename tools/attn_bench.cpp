@@ -1,6 +1,7 @@
 // attn_bench -- torch-free timing of the BERT attention core through the C ABI (mb_attention_forward / _backward), with the
 // per-block phase stamps of the backward when MB_ATTN_TRACE=1.  Measurement tooling (not product).
-//   attn_bench [--batch B] [--seq L] [--heads nh] [--reps n] [--p dropout]
+//   attn_bench [--batch B] [--seq L] [--heads nh] [--reps n] [--p dropout] [--tiled 0|1]
+// --tiled 1: the tiled pair (mb_attention_tiled_*, L <= 512; the engines' kernels for L > 128), with its row-statistics scratch
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -27,11 +28,12 @@ static void* dev_rand(size_t n_bf16, uint32_t seed) {
 }
 
 int main(int argc, char** argv) {
-    int B = 48, L = 50, nh = 12, reps = 96; float pdrop = 0.1f;
+    int B = 48, L = 50, nh = 12, reps = 96, tiled = 0; float pdrop = 0.1f;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--batch") B = atoi(argv[i + 1]); else if (k == "--seq") L = atoi(argv[i + 1]); else if (k == "--heads") nh = atoi(argv[i + 1]);
         else if (k == "--reps") reps = atoi(argv[i + 1]); else if (k == "--p") pdrop = (float)atof(argv[i + 1]);
+        else if (k == "--tiled") tiled = atoi(argv[i + 1]);
     }
     const int H = nh * 64, T = B * L, nset = 6;
     hipStream_t st; HCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -53,6 +55,16 @@ int main(int argc, char** argv) {
         float ms; HCK(hipEventElapsedTime(&ms, e0, e1));
         printf("%-28s B=%d L=%d heads=%d p=%.2f : %7.2f us/launch\n", name, B, L, nh, pdrop, ms * 1e3 / reps);
     };
+    if (tiled) {
+        std::vector<float*> stats(nset);
+        for (int s = 0; s < nset; ++s) HCK(hipMalloc(&stats[s], mb_attention_tiled_stats_bytes(B, L, nh)));
+        timeit("tiled attention forward", [&](int i) {
+            MCK(mb_attention_tiled_forward(MB_DT_BF16, qkv[i % nset], mask, ctx[i % nset], stats[i % nset], B, L, nh, &key, nullptr, nullptr, st)); });
+        timeit("tiled attention backward", [&](int i) {
+            MCK(mb_attention_tiled_backward(MB_DT_BF16, qkv[i % nset], mask, ctx[i % nset], dctx[i % nset], stats[i % nset], dqkv[i % nset],
+                                            nullptr, B, L, nh, &key, nullptr, st)); });
+        return 0;
+    }
     timeit("attention forward", [&](int i) { MCK(mb_attention_forward(MB_DT_BF16, qkv[i % nset], mask, ctx[i % nset], B, L, nh, &key, st)); });
     timeit("attention backward", [&](int i) { MCK(mb_attention_backward(MB_DT_BF16, qkv[i % nset], mask, dctx[i % nset], dqkv[i % nset], B, L, nh, &key, st)); });
     std::vector<unsigned long long> tr((size_t)8192 * 8);
