@@ -87,6 +87,8 @@ PROTOTYPES = {
     "mb_xlnet_query_stream": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _vp]),
     "mb_bert_mark_grads_zero": (_i, [_vp, _i]),
     "mb_xlnet_mark_grads_zero": (_i, [_vp, _i]),
+    "mb_bert_distrust_word_stamps": (_i, [_vp]),
+    "mb_bert_word_skip_updates": (_sz, [_vp]),
     "mb_bert_materialize_grads": (_i, [_vp, _vp]),
     "mb_xlnet_materialize_grads": (_i, [_vp, _vp]),
     "mb_bert_grads_stale": (_i, [_vp]),

@@ -510,6 +510,10 @@ class _Core(object):
         if comm is not None and opt is None:
             raise ValueError("the data-parallel single-call step ends with the optimizer (micro-steps exchange nothing)")
         extra = () if comm is None else (comm.handle,)
+        if self.kind == "bert" and self.grads._version != getattr(self, "_gz_version", -1):
+            # torch wrote into the flat gradient buffer since the engine last looked (torch_wrote_grads): the sweep of this update
+            # cannot take the word rows outside its batches for zero (include/magbert_hip.h: mb_bert_distrust_word_stamps)
+            _lib.check(self.lib.mb_bert_distrust_word_stamps(self.handle))
         with _Core._Hop(self):
             _lib.check(self._fn("train_step" if comm is None else "train_step_dp")(
                 self.handle, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5], B, L,

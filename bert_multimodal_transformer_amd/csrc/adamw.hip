@@ -135,4 +135,84 @@ int adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, s
     return (int)hipGetLastError();
 }
 
+// The end-of-step sweep of a single-call step (kernels.h AdamRanges / WordSkip): the ranges laid end to end are cut into one contiguous
+// piece per block, as adamw_var_kernel<NT, 2, true> cuts one range; a block whose piece crosses a range boundary walks both parts.
+// A quad of the word-embedding table whose row carries no stamp of this update gets g = +0.0f without the load and keeps the zero it
+// has without the store; a wave may straddle two rows (768 floats = three waves of quads), which costs a divergent load.
+template <bool NT>
+__global__ void __launch_bounds__(256) adamw_sweep_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16* __restrict__ shadow, AdamRanges R, size_t n_decay,
+                                                          size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end,
+                                                          const AdamArgs* __restrict__ dyn, WordSkip ws) {
+    constexpr int UNR = 2;
+    size_t total4 = 0;
+    for (int k = 0; k < MB_SWEEP_MAX; ++k) if (k < R.count) total4 += R.n[k] / 4;
+    const size_t per = ((total4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const size_t vb = (size_t)blockIdx.x * per, ve = min(total4, vb + per);
+    const bool skip_on = ws.stamp != nullptr && ws.state[1] != 0u;
+    const uint32_t stamp_no = skip_on ? ws.state[0] : 0u;
+    size_t off = 0;          // quads of the ranges in front of range k
+#pragma unroll 1
+    for (int k = 0; k < R.count; ++k) {
+        const size_t n4 = R.n[k] / 4;
+        const size_t lo = max(vb, off), hi = min(ve, off + n4);
+        off += n4;
+        if (lo >= hi) continue;
+        const AdamArgs a = dyn[R.slot[k]];
+        const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+        const float decay = a.lr * a.weight_decay;
+        const size_t base4 = R.begin[k] / 4 + n4 - off;          // quad index in the buffers = base4 + index in the laid-out ranges
+        const size_t begin = base4 + lo + threadIdx.x, end = base4 + hi;
+        for (size_t i4 = begin; i4 < end; i4 += 256 * UNR) {
+            AdamQuad q[UNR];
+            bool live[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const size_t i = (i4 + (size_t)u * 256) * 4;
+                live[u] = true;
+                if (i4 + (size_t)u * 256 < end) {
+                    if (skip_on && i >= ws.begin && i < ws.end) live[u] = ws.stamp[(uint32_t)(i - ws.begin) / ws.row_len] == stamp_no;
+                    q[u] = adam_load<NT>(p, g, m, v, i, live[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u)
+                if (i4 + (size_t)u * 256 < end)
+                    adam_update_store<NT>(q[u], p, g, m, v, shadow, (i4 + (size_t)u * 256) * 4, a, omb1, omb2, decay, n_decay, sh_begin, sh_end,
+                                          keep_begin, keep_end, live[u] ? 1 : 0);
+        }
+    }
+}
+
+int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const AdamRanges& r, size_t n_decay, size_t sh_begin, size_t sh_end,
+                size_t keep_begin, size_t keep_end, const AdamArgs* dyn, const WordSkip& skip, hipStream_t st) {
+    if (r.count < 0 || r.count > MB_SWEEP_MAX || !dyn) return MB_ERR_ARG;
+    size_t n = 0;
+    for (int k = 0; k < r.count; ++k) {
+        if ((r.begin[k] | r.n[k]) % 4 || r.slot[k] < 0 || r.slot[k] > 1) return MB_ERR_SHAPE;
+        n += r.n[k];
+    }
+    if (n == 0) return MB_OK;
+    if ((n_decay % 4) || (sh_begin % 4) || (sh_end % 4) || (keep_begin % 4) || (keep_end % 4)) return MB_ERR_SHAPE;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MB_ERR_SHAPE;
+    if (skip.stamp && (!skip.state || skip.row_len == 0 || (skip.begin | skip.end | skip.row_len) % 4 || skip.end < skip.begin ||
+                       skip.end - skip.begin > 0xffffffffull)) return MB_ERR_SHAPE;
+    {   // (as adamw_step: bench.py prices the step's sweep from this line -- one launch, one line)
+        static int log = -1;
+        if (log < 0) { const char* e = getenv("MB_GEMM_LOG"); log = e ? atoi(e) : 0; }
+        if (log) fprintf(stderr, "[magbert adamw] n=%zu\n", n);
+    }
+    const size_t n4 = n / 4;
+    unsigned grid = (unsigned)((n4 + 255) / 256);
+    if (grid > 256 * 16) grid = 256 * 16;
+    static int nt = -1, vgrid = 0;
+    if (nt < 0) { const char* e = getenv("MB_ADAMW_NT"); nt = e ? atoi(e) : 1; const char* g2 = getenv("MB_ADAMW_GRID"); vgrid = g2 ? atoi(g2) : 0; }
+    if (vgrid > 0 && (unsigned)vgrid < grid) grid = (unsigned)vgrid;
+    if (nt) hipLaunchKernelGGL(adamw_sweep_kernel<true>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, n_decay, sh_begin, sh_end,
+                               keep_begin, keep_end, dyn, skip);
+    else hipLaunchKernelGGL(adamw_sweep_kernel<false>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, n_decay, sh_begin, sh_end,
+                            keep_begin, keep_end, dyn, skip);
+    return (int)hipGetLastError();
+}
+
 }  // namespace mb

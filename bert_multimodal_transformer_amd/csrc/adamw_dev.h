@@ -17,6 +17,22 @@ template <bool NT> __device__ __forceinline__ AdamQuad adam_load(const float* p,
     }
     return q;
 }
+// ... whose gradient is only loaded when `live`: the caller knows it to be +0.0f otherwise (kernels.h WordSkip) and pairs this with
+// zero_grad = 0 in adam_update_store, so the quad's gradient is neither read nor written -- and the arithmetic sees the same +0.0f
+template <bool NT> __device__ __forceinline__ AdamQuad adam_load(const float* p, const float* g, const float* m, const float* v, size_t i, bool live) {
+    AdamQuad q;
+    q.g = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (NT) {
+        q.p = __builtin_nontemporal_load((const f32x4*)(p + i));
+        if (live) q.g = __builtin_nontemporal_load((const f32x4*)(g + i));
+        q.m = __builtin_nontemporal_load((const f32x4*)(m + i)); q.v = __builtin_nontemporal_load((const f32x4*)(v + i));
+    } else {
+        q.p = *(const f32x4*)(p + i);
+        if (live) q.g = *(const f32x4*)(g + i);
+        q.m = *(const f32x4*)(m + i); q.v = *(const f32x4*)(v + i);
+    }
+    return q;
+}
 template <bool NT> __device__ __forceinline__ void adam_update_store(AdamQuad q, float* p, float* g, float* m, float* v, bf16* shadow, size_t i,
                                                                      const AdamArgs& a, float omb1, float omb2, float decay, size_t n_decay,
                                                                      size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, int zero_grad) {

@@ -67,6 +67,7 @@ struct mb_bert_engine : StepMixin {
     int adam_ride = 1, ride_blocks = 0;
     float* ride_m = nullptr; float* ride_v = nullptr;       // Adam moments of the step being enqueued, when riders apply to it
     size_t ride_cursor = 0;                                 // the riders of the step being enqueued have taken [ride_cursor, wp) of the decay slab
+    bool one_sweep = true;                                  // MB_ADAMW_ONE_SWEEP=0: the end-of-step sweep as three launches (kernels.h AdamRanges)
     long ride_params = 0;                                   // MB_ADAMW_RIDE_PARAMS: parameters per launch (0 = by the token count)
     // MB_ADAMW_RIDE_DGRAD >= 1: riders also in the two 64 x 64 dgrad launches of a layer (ffn1, qkv: 456 tiles in 768 block slots at T = 2400;
     // kernels.h gemm_nn_ride_launch), 2 (default): and in the 128 x 128 ffn2 dgrad (456 tiles in 512 slots: 56 CUs hold one tile).
@@ -206,6 +207,11 @@ static void build_layout(mb_bert_engine* e) {
     e->carve_step(w, T, (int)V, (int)A, c.max_batch, c.num_labels, SITE_LAYER0 + 4 * c.num_layers);
     e->idcnt_off = w.take((size_t)c.vocab_size * 4);          // token-id occurrence table of the single-call step (MB_EMBED_UNIQUE=0: off)
     { const char* uv = getenv("MB_EMBED_UNIQUE"); e->idcnt_enable = !(uv && atoi(uv) == 0); }
+    // stamps of the word rows a step touched + the sweep's two state words (StepMixin::stamp_live; MB_ADAMW_SKIP_ZERO_ROWS=0: full read)
+    e->stamp_rows = (size_t)c.vocab_size;
+    e->stamp_off = w.take(((size_t)c.vocab_size + 2) * 4);
+    { const char* sv = getenv("MB_ADAMW_SKIP_ZERO_ROWS"); e->stamp_enable = !(sv && atoi(sv) == 0); }
+    { const char* ov = getenv("MB_ADAMW_ONE_SWEEP"); e->one_sweep = !(ov && atoi(ov) == 0); }
     if (e->deterministic) {          // shadow accumulator of everything behind the layers' GEMM weights (those have ONE writer per element)
         e->det_begin = e->wp; e->det_end = e->n_params;
         e->ws_det = w.take((e->det_end - e->det_begin) * sizeof(long long));
@@ -484,6 +490,7 @@ int mb_bert_bind(mb_bert_engine* e, float* params, float* grads, void* shadow, v
     if (e->c.dtype == DT_BF16 && !shadow) return MB_ERR_ARG;
     e->P = params; e->G = grads; e->SH = (char*)shadow; e->ws = (char*)workspace;
     e->grads_zero = false;                 // a newly bound gradient buffer: nothing is known about its contents
+    e->stamp_live = e->word_zero = false; e->sweep_no = 1;      // (and a workspace that is cleared before its first pass)
     e->ws_zeroed = false; e->padT = -1;
     e->drop_graphs();                         // captured against the old buffers
     char* mws = e->ws + e->ws_mag;
@@ -584,6 +591,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
     hipStream_t st = (hipStream_t)stream;
     const mb_bert_config& c = e->c;
     if (!e->G || !e->ran_forward) return MB_ERR_ARG;
+    if (!e->in_step) e->stamp_live = e->word_zero = false;          // an explicit backward (any stage of it): word rows nobody stamped get a gradient
     const int dt = c.dtype, H = c.hidden_size, I = c.intermediate_size, B = e->B, L = e->L, T = B * L, nh = c.num_heads;
     const int NL = c.num_layers;
     const int Tk = (int)align_up((size_t)T, 64);      // zero-padded reduction length of the wgrad GEMMs
@@ -603,6 +611,10 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
         e->ride_cursor = rb;
         return r;
     };
+    // (Riders in the tail of the step -- layer 0's GEMM weights, final behind the layer's qkv dgrad, as 152 workgroups in front of the 360
+    //  tiles of MAG's grouped 64 x 64 weight-gradient launch, a symbol of its own at 146 registers -- were built and measured: no gain at
+    //  any budget from 1 M to 7 M parameters, 3.245 ms without | 3.249 - 3.257 with, same box: profiles/sweep_tail_budget.txt.  That
+    //  launch is k-loop latency on every CU, not idle CUs.)
     // (Riders in the LayerNorm-backward launches -- 150 latency-bound workgroups on 256 CUs, 24 launches per step -- were built and
     //  measured: no gain at any budget, +0.09 ms when they replace the weight-gradient riders: profiles/r06_adamw_ride_ln.txt.  What
     //  pays is a CU that has NOTHING else to do for tens of microseconds.)
@@ -914,6 +926,33 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_params;
         CK(e->prof_mark(2 * NL, st));
+        // The sweep proper: what the riders left of the layers, the rest of the decay slab, the no-decay slab.  ONE launch over that list
+        // (kernels.h AdamRanges; MB_ADAMW_ONE_SWEEP=0: one launch per range), which leaves the gradients of the word rows this update's
+        // batches did not touch alone when the engine can vouch for their zeros (WordSkip, StepMixin::stamp_live: the prologue put the
+        // verdict of THIS step into device memory, so the captured launch is the same either way).  Both off: the three launches below.
+        const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
+        if (nseg == 1 && (e->one_sweep || skip)) {
+            AdamRanges all = {};
+            auto add = [&](size_t b, size_t en, int slot) {
+                if (en > b) { all.begin[all.count] = b; all.n[all.count] = en - b; all.slot[all.count] = slot; ++all.count; }
+            };
+            if (ride) add(0, e->ride_cursor, 0);
+            add((!fuse && !ride) ? 0 : e->wp, nd, 0);
+            add(nd, n, 1);
+            const bool keep = e->keep_in_step();
+            WordSkip ws_ = {};
+            if (skip) ws_ = WordSkip{e->stamp_table(ws), e->stamp_state(ws), e->word, e->word + (size_t)e->c.vocab_size * e->c.hidden_size,
+                                      (uint32_t)e->c.hidden_size};
+            void* sh = e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr;
+            for (int k = 0; k < (e->one_sweep ? 1 : all.count); ++k) {
+                AdamRanges one = all;
+                if (!e->one_sweep) { one = AdamRanges{}; one.begin[0] = all.begin[k]; one.n[0] = all.n[k]; one.slot[0] = all.slot[k]; one.count = 1; }
+                CK(adamw_sweep(e->P, e->G, m, v, sh, one, nd, e->sh_begin, e->sh_end, keep ? e->stale_begin : 0, keep ? e->stale_end : 0,
+                               e->adam_state(ws), ws_, st));
+            }
+            CK(e->prof_mark(2 * NL + 1, st));
+            return MB_OK;
+        }
         // (with chunks on the side stream, what is left of the decay slab: the pooler weight .. the classifier weight)
         if (ride) CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));       // what no launch carried (layer 0 always)
         CK(adamw_decay_range(e, m, v, (nseg == 1 && !fuse && !ride) ? 0 : e->wp, nd, st));
@@ -1203,9 +1242,16 @@ int mb_bert_set_attention_output(mb_bert_engine* e, float* probs) {
 int mb_bert_mark_grads_zero(mb_bert_engine* e, int known_zero) {
     if (!e) return MB_ERR_ARG;
     e->grads_zero = known_zero != 0;
+    if (!known_zero) e->stamp_live = e->word_zero = false;      // somebody else is writing gradients (StepMixin::stamp_live)
     if (known_zero) e->grads_stale = false;       // the caller zeroed the whole buffer itself
     return MB_OK;
 }
+int mb_bert_distrust_word_stamps(mb_bert_engine* e) {
+    if (!e) return MB_ERR_ARG;
+    e->stamp_live = e->word_zero = false;
+    return MB_OK;
+}
+size_t mb_bert_word_skip_updates(const mb_bert_engine* e) { return e ? e->skip_updates : 0; }
 int mb_bert_materialize_grads(mb_bert_engine* e, void* stream) {
     if (!e) return MB_ERR_ARG;
     return e->materialize_grads(e->G, (hipStream_t)stream);

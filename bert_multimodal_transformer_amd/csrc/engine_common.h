@@ -219,6 +219,21 @@ struct StepMixin {
     // single-call step: the prologue counts the occurrences of every token id (workspace offset of the table, 0 = none); `counted`
     // tells the engine's backward that the table describes the batch of this step
     size_t idcnt_off = 0; bool idcnt_enable = false, counted = false;
+    // Untouched word rows (kernels.h WordSkip; MB_ADAMW_SKIP_ZERO_ROWS=0: off).  stamp_off: workspace offset of the vocab-sized stamp table
+    // followed by the two state words (0 = this engine has none); sweep_no: the number of the next optimizer update, counted on the host
+    // (train_step_impl runs for every step, replayed or not) and never 0, the table's initial value.
+    // stamp_live is the proof the sweep needs: "every word-row gradient was +0.0f at some point, and every backward since then belonged
+    // to a single-call step whose prologue stamped its batch with sweep_no".  word_zero is the first half: set only by the engine's own
+    // single-call step that ended with the optimizer (its sweep covers the word table and stores the zeros); a caller's claim
+    // (mb_*_mark_grads_zero) is about the layers' weight gradients and is not taken for it.  A step that finds word_zero set starts a
+    // window, gradient-accumulation micro-steps keep it, and everything else that may write gradients ends both: a backward outside
+    // such a step, a stage-driven step, mb_*_mark_grads_zero(0), a newly bound buffer, a step that failed, mb_*_distrust_word_stamps
+    // (the Python mirror: torch wrote into the buffer).  Without the proof the sweep reads every gradient, and proves it anew.
+    size_t stamp_off = 0, stamp_rows = 0; bool stamp_enable = false, stamp_live = false, word_zero = false;
+    uint32_t sweep_no = 1;
+    size_t skip_updates = 0;       // updates enqueued with the proof in hand (mb_*_word_skip_updates: what the tests look at)
+    uint32_t* stamp_table(char* ws) const { return (uint32_t*)(ws + stamp_off); }
+    uint32_t* stamp_state(char* ws) const { return stamp_table(ws) + stamp_rows; }
     bool loss_cleared = false;     // single-call step: the step prologue clears the loss accumulator (no zero_fill launch in the forward)
     bool capturing = false;        // the stream is in capture mode: nothing outside the captured sequence may be waited for
     int nsites = 0;
@@ -278,6 +293,7 @@ struct StepMixin {
     }
     int begin_backward_pass(float* G, hipStream_t st) {
         if (in_step) return MB_OK;           // the single-call step decided already (and replays a graph captured for that decision)
+        stamp_live = word_zero = false;      // a backward nobody stamped
         ow_pass = grads_zero && ow_enable;
         grads_zero = false;
         if (!(ow_pass && ow_covers)) CK(materialize_grads(G, st));      // this pass adds onto the range: it needs the zeros
@@ -334,6 +350,7 @@ struct StepMixin {
                         int mode, hipStream_t st, Enq enqueue) {
         struct Scope { StepMixin* m; ~Scope() { m->dyn = false; m->capturing = false; m->in_step = false; m->stage_mode = false; } } scope{this};
         dyn = true; in_step = true; stage_mode = true;
+        stamp_live = word_zero = false;      // (the stage-driven step's prologue stamps nothing)
         if (mode == 2) return enqueue(st);
         StageGraph* g = nullptr;
         for (auto& x : stage_graphs)
@@ -419,8 +436,19 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
             e->in_step = false; e->loss_cleared = false; e->packed = false; e->packed_w = false; e->counted = false;
             e->grads_zero = ok && with_opt;
             e->grads_stale = ok ? (with_opt && e->keep_in_step()) : stale_before;
+            // an update was enqueued: its sweep left every word gradient zero, and the next batch is stamped with the next number
+            if (ok && with_opt && e->stamp_live) ++e->skip_updates;
+            if (!ok || with_opt) e->stamp_live = false;
+            e->word_zero = ok && with_opt;
+            if (ok && with_opt && ++e->sweep_no == 0u) e->sweep_no = 1u;
         }
     } flags{e, false, m != nullptr, stale_before};
+    // untouched word rows (StepMixin::stamp_live): this step's prologue stamps its batch, so a window that is live stays live, and
+    // word gradients the engine itself left all zero open one
+    const bool stamping = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable && ids != nullptr;
+    if (!stamping) e->stamp_live = false;
+    else if (e->word_zero) e->stamp_live = true;
+    e->word_zero = false;                   // (this step's backward writes some of them)
     e->in_step = true; e->ow_pass = ow != 0;
     auto enqueue = [&](int sg, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
         return enqueue_inner(sg, lg, ls, lr_, m_, v_, sc, s);
@@ -434,6 +462,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     pa.zero_dw = (uint32_t*)loss; e->loss_cleared = loss != nullptr;
     if (e->idcnt_enable && ids) { pa.ids = (const int64_t*)ids; pa.n_ids = B * L; pa.id_count = (int*)(ws + e->idcnt_off); }
     e->counted = pa.id_count != nullptr;
+    if (stamping) { pa.stamp = e->stamp_table(ws); pa.stamp_state = e->stamp_state(ws); pa.stamp_no = e->sweep_no; pa.stamp_on = e->stamp_live ? 1u : 0u; }
     if (m) {
         double ss = lr;
         if (correct_bias) ss = (double)lr * sqrt(1.0 - pow((double)beta2, (double)opt_step)) / (1.0 - pow((double)beta1, (double)opt_step));

@@ -275,6 +275,19 @@ int head_backward(int dtype, const float* dlogits, const float* logits, const fl
 int adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, size_t n_decay,
                size_t sh_begin, size_t sh_end, AdamArgs a, int zero_grad, hipStream_t st, const AdamArgs* dyn = nullptr,
                size_t keep_begin = 0, size_t keep_end = 0);
+// The end-of-step sweep of a single-call step as ONE launch over a short list of ranges of the flat buffers (three launches otherwise:
+// what the riders left of the layers, the rest of the decay slab, the no-decay slab).  Everything is ABSOLUTE here: p / g / m / v /
+// shadow are the buffers' first elements; ranges, n_decay, the shadow and keep ranges are element offsets (multiples of 4) into them;
+// range k reads its scalars from dyn[slot[k]].  Same per-element arithmetic as adamw_step (adam_update_store): the same bits.
+#define MB_SWEEP_MAX 4
+struct AdamRanges { size_t begin[MB_SWEEP_MAX], n[MB_SWEEP_MAX]; int slot[MB_SWEEP_MAX]; int count; };
+// Word-embedding rows the step did not touch (MB_ADAMW_SKIP_ZERO_ROWS): stamp[row] == state[0] <=> the prologue of a step whose
+// backward feeds this update saw `row` in its batch (PrologueArgs::stamp).  When state[1] != 0 the engine vouches that every other row
+// of [begin, end) -- rows of `row_len` elements -- holds g == +0.0f: the sweep neither loads that gradient nor stores the zero back,
+// and runs the same arithmetic on a +0.0f it makes up.  state[1] == 0: the full read (decided per step, so a replayed graph obeys it).
+struct WordSkip { const uint32_t* stamp; const uint32_t* state; size_t begin, end; uint32_t row_len; };
+int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const AdamRanges& r, size_t n_decay, size_t sh_begin, size_t sh_end,
+                size_t keep_begin, size_t keep_end, const AdamArgs* dyn, const WordSkip& skip, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------ step prologue (rowops.hip)
 // Everything that changes from one optimizer step to the next, moved into device memory by ONE small launch so that the rest
@@ -294,6 +307,9 @@ struct PrologueArgs {
     struct PackJob { const float* src; void* dst; int rows, cols, pitch, dtype; } pack[2];
     int npack;
     const int64_t* ids; int n_ids; int* id_count;     // id_count[ids[i]] += 1 (see embed_ln_backward), may be null
+    // stamp[ids[i]] = stamp_no, the number of the optimizer update that will consume this batch's gradients, and stamp_state[0 .. 1] =
+    // {stamp_no, stamp_on} for the sweep of that update (WordSkip above); never cleared, right under graph replay.  May be null
+    uint32_t* stamp; uint32_t* stamp_state; uint32_t stamp_no, stamp_on;
     // MAG's weights packed into the operands of its regrouped GEMMs (mag_pack.h) by EXTRA blocks of this launch, which is waiting for
     // PCIe anyway: the first `copy_blocks` blocks (filled by step_prologue) do everything above, the rest this.  W_hv == null: none
     struct MagPackW { const float* W_hv; const float* W_ha; const float* W_v; const float* W_a; void* We; void* Wv; void* Wa; MagDims d; int dtype; } magw;

@@ -787,6 +787,11 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
     // here because this launch waits for PCIe anyway (inside embed_fwd the 2,400 device-scope atomics cost 10 us)
     if (a.id_count != nullptr)
         for (size_t i = tid; i < (size_t)a.n_ids; i += nth) atomicAdd(a.id_count + a.ids[i], 1);
+    // ... and which word rows the coming optimizer update will find a gradient in (kernels.h WordSkip: every writer stores the same number)
+    if (a.stamp != nullptr) {
+        for (size_t i = tid; i < (size_t)a.n_ids; i += nth) a.stamp[a.ids[i]] = a.stamp_no;
+        if (tid < 2) a.stamp_state[tid] = tid == 0 ? a.stamp_no : a.stamp_on;
+    }
     for (int k = 0; k < a.npack; ++k) {          // (before the copies: these loads cross PCIe too and should be in flight with them)
         const PrologueArgs::PackJob& j = a.pack[k];
         const size_t n = (size_t)j.rows * j.cols;
@@ -852,6 +857,7 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
 int step_prologue(const PrologueArgs& a, hipStream_t st) {
     if (a.ncopies < 0 || a.ncopies > MB_PROLOGUE_MAX_COPIES || a.nsites < 0 || (a.nsites > 0 && !a.keys)) return MB_ERR_ARG;
     if (a.npack < 0 || a.npack > 2) return MB_ERR_ARG;
+    if (a.stamp && (!a.stamp_state || !a.ids)) return MB_ERR_ARG;
     size_t most = 0;
     for (int k = 0; k < a.npack; ++k) {
         if (!a.pack[k].src || !a.pack[k].dst || a.pack[k].cols < 1 || a.pack[k].pitch < a.pack[k].cols) return MB_ERR_ARG;

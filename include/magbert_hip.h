@@ -212,6 +212,14 @@ int mb_bert_stage_grad_ranges(const mb_bert_engine* e, int stage, size_t* offs, 
  * mb_adamw_step with zero_grad) says so with known_zero = 1; anything else that writes gradients must leave / set it 0.  The
  * flag is consumed by the first stage of the next backward.  MB_WGRAD_OVERWRITE=0 disables the optimisation. */
 int mb_bert_mark_grads_zero(mb_bert_engine* e, int known_zero);
+/* Untouched word-embedding rows.  The sweep at the end of mb_bert_train_step does not read the gradient of a word row that no batch
+ * of this update contained, when the engine can prove it is +0.0f: its own previous single-call step zeroed the table, and every
+ * backward since went through a single-call step (gradient-accumulation micro-steps included).  The engine notices its own other
+ * backwards and mb_bert_mark_grads_zero(e, 0); a host that writes into the bound gradient buffer by any other way between two
+ * single-call steps calls this (or mb_bert_mark_grads_zero(e, 0)) before the next one, whose update then reads every gradient.
+ * MB_ADAMW_SKIP_ZERO_ROWS=0 disables the skip; never needed when the host does not touch the buffer. */
+int mb_bert_distrust_word_stamps(mb_bert_engine* e);
+size_t mb_bert_word_skip_updates(const mb_bert_engine* e);      /* updates whose sweep was allowed to skip, since the engine was created */
 /* Lazy zeroing.  The zeros mb_bert_train_step's AdamW would write over the layers' GEMM weight gradients are only ever
  * overwritten by the next backward, so a step that ends with the optimizer leaves that range "logically zero, physically stale"
  * (the rest of the buffer IS zeroed).  The engine writes the zeros itself before any of its own backwards that accumulates;

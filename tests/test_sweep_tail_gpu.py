@@ -1,0 +1,157 @@
+"""GPU: the end-of-step AdamW sweep of the single-call MAG-BERT step as ONE launch over its ranges (MB_ADAMW_ONE_SWEEP, csrc/kernels.h
+AdamRanges) that leaves alone the gradient of word-embedding rows no batch of the update touched (MB_ADAMW_SKIP_ZERO_ROWS, csrc/kernels.h
+WordSkip, csrc/engine_common.h StepMixin::stamp_live).
+
+Same per-element arithmetic on a +0.0f the kernel makes up instead of the +0.0f it would have loaded, so nothing may change: in
+deterministic mode (MB_DETERMINISTIC=1) every trajectory below ends with the SAME BITS in the parameters, both Adam moments, the bf16
+shadow and the logits whether the two switches are on or off, the gradient buffer reads all zero, and the graph statistics are equal.
+torch.equal throughout: there is no tolerance to state.  Every case also checks that the skip was really in force for the updates where
+the engine can prove its invariant (mb_bert_word_skip_updates) and for no other."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from bert_multimodal_transformer_amd import (AdamW, BertConfig, MAG_BertForSequenceClassification, MultimodalConfig,
+                                             get_linear_schedule_with_warmup)
+from oracle import weights
+
+DEV = "cuda:0"
+KEYS = ("p", "m", "v", "shadow", "logits")
+
+
+def _build(cdt, layers=3):
+    cfg = BertConfig(num_hidden_layers=layers, num_labels=1, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
+    m = MAG_BertForSequenceClassification(cfg, MultimodalConfig(1.0, 0.5), visual_dim=47, acoustic_dim=74, compute_dtype=cdt)
+    m.load_state_dict({n: torch.from_numpy(weights.make_param(n, tuple(p.shape), "test")) for n, p in m.named_parameters()})
+    return m
+
+
+def _batch(B, L, seed):
+    return weights.synthetic_bert_batch(B, L, 47, 74, seed=seed)
+
+
+def _odd_batch(B, L, seed):
+    """one id occurs twice in a sample (and nowhere else), and sample 0 is all padding: ids 0, mask 0, zero modality rows"""
+    b = _batch(B, L, seed)
+    b["input_ids"][1, 2] = b["input_ids"][1, 1]
+    b["input_ids"][0, :] = 0
+    b["input_mask"][0, :] = 0
+    b["visual"][0] = 0
+    b["acoustic"][0] = 0
+    assert int((b["input_ids"] == b["input_ids"][1, 1]).sum()) == 2
+    return b
+
+
+def _dev(b):
+    t = lambda k: torch.from_numpy(b[k]).to(DEV)
+    return t("input_ids"), t("visual"), t("acoustic"), t("input_mask"), t("segment_ids"), t("label_ids")
+
+
+def _run(monkeypatch, cdt, on, batches, accum=1, mode=True, unfused=()):
+    """len(batches) / accum optimizer updates (dropout on, schedule moving) through model.train_step.  mode: True = prologue + replayed
+    graph (mode 1), 2 = prologue + the same launches one by one; unfused: indices of the updates taken through training_step +
+    optimizer.step() instead (accum == 1 only)."""
+    from bert_multimodal_transformer_amd.multimodal_driver import optimizer_grouped_parameters
+    monkeypatch.setenv("MB_DETERMINISTIC", "1")
+    monkeypatch.setenv("MB_ADAMW_SKIP_ZERO_ROWS", "1" if on else "0")
+    monkeypatch.setenv("MB_ADAMW_ONE_SWEEP", "1" if on else "0")
+    torch.manual_seed(77)
+    m = _build(cdt).train()
+    opt = AdamW(optimizer_grouped_parameters(m), lr=1e-3)
+    sch = get_linear_schedule_with_warmup(opt, num_warmup_steps=1.0, num_training_steps=10)
+    core = m._core
+    with m.stream_scope():
+        for s, b in enumerate(batches):
+            ids, vis, aco, mask, seg, lab = _dev(b)
+            update = (s + 1) % accum == 0
+            if mode == 2:
+                o = opt.flat_step_args(core) if update else None
+                if update:
+                    opt._t += 1
+                    o["t"] = opt._t
+                core.train_step(ids, vis, aco, mask, seg, lab, o, loss_scale=1.0 / accum, mode=2)
+            else:
+                graph = False if (s // accum) in unfused else True
+                m.train_step(ids, vis, aco, mask, seg, lab, optimizer=opt if update else None, loss_scale=1.0 / accum, graph=graph)
+            if update:
+                sch.step()
+    stats = core.graph_stats()
+    skipped = int(core.lib.mb_bert_word_skip_updates(core.handle))
+    m.eval()
+    ids, vis, aco, mask, seg, lab = _dev(_batch(4, 40, 99))
+    with torch.no_grad():
+        logits = m(ids, vis, aco, token_type_ids=seg, attention_mask=mask)[0].clone()
+    torch.cuda.synchronize()
+    return dict(p=m.flat_params.clone(), m=core._adam_m.clone(), v=core._adam_v.clone(), g=m.flat_grads.clone(), logits=logits,
+                shadow=core.shadow.clone(), stats=stats, skipped=skipped)
+
+
+def _same(new, ref, what):
+    for k in KEYS:
+        assert torch.equal(new[k], ref[k]), "%s: %s differs" % (what, k)
+    assert float(new["g"].abs().max()) == 0.0 and float(ref["g"].abs().max()) == 0.0, "%s: gradients left behind" % what
+
+
+# (the largest shape first: a larger batch later would re-create the engine, and with it the counter this file looks at)
+SHAPES = ((48, 50), (24, 50), (5, 40), (48, 50))
+
+
+@pytest.mark.parametrize("cdt", [torch.bfloat16, torch.float32])
+def test_one_sweep_that_skips_untouched_word_rows_changes_nothing(cdt, monkeypatch):
+    """four updates over three shapes (three graphs captured, one replayed), both dtypes.  The first update has no proof that the word
+    gradients start from zero (nothing of the engine's own has swept them yet) and reads everything; the other three skip."""
+    batches = [_batch(B, L, 90 + s) for s, (B, L) in enumerate(SHAPES)]
+    off = _run(monkeypatch, cdt, False, batches)
+    on = _run(monkeypatch, cdt, True, batches)
+    _same(on, off, "switches on vs off")
+    assert on["stats"] == off["stats"] and on["stats"][0] == 3 and on["stats"][1] == 4, (on["stats"], off["stats"])
+    assert off["skipped"] == 0 and on["skipped"] == 3, (off["skipped"], on["skipped"])
+
+
+def test_rows_touched_by_an_earlier_micro_step_only_are_not_skipped(monkeypatch):
+    """accum = 2: a row that only the FIRST micro-batch of an update touched holds a gradient when the sweep runs, although the batch of
+    the step that carries the sweep does not contain it -- every micro-step's prologue stamps with the number of the update to come."""
+    batches = [_batch(B, L, 190 + s) for s, (B, L) in enumerate(SHAPES + SHAPES)]
+    for u in range(4):
+        first, second = (set(np.unique(batches[2 * u + k]["input_ids"]).tolist()) for k in (0, 1))
+        assert first - second, "update %d: every id of the first micro-batch is in the second one too" % u
+    off = _run(monkeypatch, torch.bfloat16, False, batches, accum=2)
+    on = _run(monkeypatch, torch.bfloat16, True, batches, accum=2)
+    _same(on, off, "accum = 2, switches on vs off")
+    assert on["stats"] == off["stats"]
+    assert off["skipped"] == 0 and on["skipped"] == 3, (off["skipped"], on["skipped"])
+
+
+def test_a_repeated_id_and_an_all_padding_sample(monkeypatch):
+    """an id that occurs twice (the embedding backward's atomic path) and a sample of nothing but [PAD] (row 0 of the table gets the
+    gradient of 40 + tokens), in updates where the skip is in force"""
+    batches = [_batch(48, 50, 290), _odd_batch(5, 40, 291), _batch(24, 50, 292), _odd_batch(5, 40, 293)]
+    off = _run(monkeypatch, torch.bfloat16, False, batches)
+    on = _run(monkeypatch, torch.bfloat16, True, batches)
+    _same(on, off, "odd batches, switches on vs off")
+    assert on["stats"] == off["stats"]
+    assert off["skipped"] == 0 and on["skipped"] == 3, (off["skipped"], on["skipped"])
+
+
+def test_launch_by_launch_step_equals_the_replayed_one(monkeypatch):
+    """mode 2 (prologue + eager launches) against mode 1 (prologue + replayed graph), switches on, and against the switches off"""
+    batches = [_batch(B, L, 390 + s) for s, (B, L) in enumerate(SHAPES)]
+    off = _run(monkeypatch, torch.bfloat16, False, batches)
+    graph = _run(monkeypatch, torch.bfloat16, True, batches)
+    eager = _run(monkeypatch, torch.bfloat16, True, batches, mode=2)
+    _same(eager, graph, "mode 2 vs mode 1")
+    _same(eager, off, "mode 2, switches on vs mode 1, switches off")
+    assert eager["stats"] == (0, 0) and eager["skipped"] == 3 and graph["skipped"] == 3, (eager["stats"], eager["skipped"], graph["skipped"])
+
+
+def test_an_update_outside_the_single_call_step_is_noticed(monkeypatch):
+    """update 1 of 4 goes through training_step + optimizer.step(): its backward stamps nothing, so update 2 cannot take the word rows
+    outside its batch for zero -- whatever the optimizer in between says it zeroed -- and reads them all; update 3 skips again."""
+    batches = [_batch(B, L, 490 + s) for s, (B, L) in enumerate(SHAPES)]
+    off = _run(monkeypatch, torch.bfloat16, False, batches, unfused=(1,))
+    on = _run(monkeypatch, torch.bfloat16, True, batches, unfused=(1,))
+    _same(on, off, "an unfused update in between, switches on vs off")
+    assert on["stats"] == off["stats"]
+    assert off["skipped"] == 0 and on["skipped"] == 1, (off["skipped"], on["skipped"])
