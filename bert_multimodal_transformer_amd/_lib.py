@@ -79,6 +79,13 @@ PROTOTYPES = {
     "mb_debug_gemm_trace": (_i, [_vp, _i]),
     "mb_debug_attention_trace": (_i, [_vp, _i]),
     "mb_xlnet_attention_probs": (_vp, [_vp, _i, C.POINTER(_i)]),
+    "mb_xlnet_attention_probs_into": (_i, [_vp, _i, _vp, _vp]),
+    "mb_xlnet_attention_tiled_stats_bytes": (_sz, [_i, _i, _i]),
+    "mb_xlnet_attention_tiled_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "mb_xlnet_attention_tiled_forward": (_i, [_i] + [_vp] * 10 + [_i, _i, _i, _dk, _vp, _vp, _i, _vp, _vp]),
+    "mb_xlnet_attention_tiled_backward": (_i, [_i] + [_vp] * 19 + [_i, _i, _i, _dk, _vp, _vp, _vp]),
+    "mb_xlnet_attention_forward": (_i, [_i] + [_vp] * 11 + [_i, _i, _i, _dk, _vp, _vp, _i, _vp]),
+    "mb_xlnet_attention_backward": (_i, [_i] + [_vp] * 20 + [_i, _i, _i, _dk, _vp, _vp, _vp]),
     "mb_xlnet_set_head_mask": (_i, [_vp, _vp]),
     "mb_xlnet_set_perm_mask": (_i, [_vp, _vp]),
     "mb_xlnet_set_mems": (_i, [_vp, _vp, _i]),

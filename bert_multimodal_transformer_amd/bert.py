@@ -118,6 +118,19 @@ def _seq_limit(config, max_seq_length):
     return max(n, 128)
 
 
+XLNET_MAX_SEQ = 512       # the tiled relative-attention kernels' limit (XLNet has no position table)
+
+
+def _xl_seq_limit(max_seq_length):
+    """the same for MAG-XLNet: None or <= 128 means 128, at most XLNET_MAX_SEQ (with mems the limit is on klen = mlen + seq_len)"""
+    if max_seq_length is None:
+        return 128
+    n = int(max_seq_length)
+    if n < 1 or n > XLNET_MAX_SEQ:
+        raise ValueError("max_seq_length = %d: must be in [1, %d]" % (n, XLNET_MAX_SEQ))
+    return max(n, 128)
+
+
 class _Core(object):
     """Flat parameter/gradient storage + engine handle shared by the model classes."""
 
@@ -125,11 +138,9 @@ class _Core(object):
                  injection_index=1, max_seq_length=None):
         self.kind = kind                     # "bert" (mb_bert_*) or "xlnet" (mb_xlnet_*)
         self.injection_index = injection_index
-        # MAG-BERT: the longest sequence this instance runs -- None or <= 128 keeps the limit of 128, above it the engine's attention
-        # runs the tiled kernels (up to the position table); MAG-XLNet keeps its own limit in the library
-        self.max_seq_length = None
-        if kind == "bert":
-            self.max_seq_length = _seq_limit(config, max_seq_length)
+        # the longest sequence this instance runs (both models) -- None or <= 128 keeps the limit of 128, above it the engine's attention
+        # runs the tiled kernels (up to the position table; MAG-XLNet, which has no table: up to the kernels' 512)
+        self.max_seq_length = _seq_limit(config, max_seq_length) if kind == "bert" else _xl_seq_limit(max_seq_length)
         if not torch.cuda.is_available():
             raise _lib.MagbertError("MAG-BERT runs on the HIP path only: no ROCm device visible (no CPU fallback)")
         self.lib = _lib.lib()
@@ -231,10 +242,11 @@ class _Core(object):
         # on its own -- piece by piece when the sharded update cut its forward (a full join here would undo that overlap)
         if join:
             self._comm_join()
-        if self.max_seq_length is not None and L > self.max_seq_length:
+        if L > self.max_seq_length:          # (never None: both kinds refuse here, before an engine is re-created)
             raise _lib.MagbertError("magbert: unsupported shape or alignment: L = %d is above this model's max_seq_length = %d "
                                     "(construct it with max_seq_length=%d, at most %d)"
-                                    % (L, self.max_seq_length, L, self.config.max_position_embeddings))
+                                    % (L, self.max_seq_length, L,
+                                       self.config.max_position_embeddings if self.kind == "bert" else XLNET_MAX_SEQ))
         if B > self.max_B or L > self.max_L or self.ws is None:
             # "logically zero, physically stale" gradients are a fact only the OLD engine knows: make them real zeros before it goes
             self.materialize_grads()
@@ -582,13 +594,19 @@ class _Core(object):
         es = 2 if self.dt == _lib.DT_BF16 else 4
         out = []
         for l in range(self.n_layers):
-            lp = C.c_int()
-            ptr = self.lib.mb_xlnet_attention_probs(self.handle, l, C.byref(lp))
-            if not ptr:
-                raise _lib.MagbertError("no forward has run")
-            LP = lp.value
-            off = ptr - self.ws.data_ptr()
-            a = self.ws[off: off + B * nh * LP * LP * es].view(self.compute_dtype).view(B, nh, LP, LP)[:, :, :L, :L].float()
+            if self.max_L > 128:
+                # an engine built for long sequences (max_L IS the engine's max_seq: _make_engine creates it with exactly that) serves
+                # no saved probabilities: they are recomputed from what the forward left
+                a = torch.empty(B, nh, L, L, dtype=torch.float32, device=self.device)
+                _lib.check(self.lib.mb_xlnet_attention_probs_into(self.handle, l, _lib.ptr(a), self.stream()))
+            else:
+                lp = C.c_int()
+                ptr = self.lib.mb_xlnet_attention_probs(self.handle, l, C.byref(lp))
+                if not ptr:
+                    raise _lib.MagbertError("no forward has run")
+                LP = lp.value
+                off = ptr - self.ws.data_ptr()
+                a = self.ws[off: off + B * nh * LP * LP * es].view(self.compute_dtype).view(B, nh, LP, LP)[:, :, :L, :L].float()
             if training and p > 0.0:
                 key = rng.make_key(self.seed, self.step, rng.XS_LAYER0 + 8 * l, p)
                 a = a * torch.from_numpy(rng.keep_mult(B * nh * L * L, key)).view(B, nh, L, L).to(a.device)

@@ -220,20 +220,41 @@ int attention_backward_free_slots(int dtype, int L, int nblk, int cus);      // 
 int attention_trace_fetch(unsigned long long* host_out, int max_blocks);     // MB_ATTN_TRACE=1: stamps of the last attention_backward
 
 // ------------------------------------------------------------------------------------------ XLNet (xlnet_attention.hip, xlnet_rowops.hip)
-// relative attention core, L <= 128.  qkv [T][3H] token-major, kr [B][2L][H], psave/gsave [B][nh][LP][LP] (LP = 32 | 64 | 128 >= L).
+// relative attention core.  qkv [T][3H] token-major, kr [B][2L][H].  L <= 128: the LDS-resident kernels, psave/gsave [B][nh][LP][LP]
+// (LP = 32 | 64 | 128 >= L).  128 < L <= 512: the tiled kernels (xlnet_attention_tiled.hip) -- psave is not touched, the forward leaves
+// row statistics in `stats`, the backward needs them, the forward's `vec`, `perm` again (it recomputes the scores) and two scratch planes
+// gsave / pdsave of xlnet_tiled_scratch_elems(B, L, nh) elements each; it takes no riders (MB_ERR_MODE).
 int xlnet_attention_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
                             const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
                             void* psave, int B, int L, int nh, DropKey drop, hipStream_t st, const float* head_scale = nullptr,
                             const uint8_t* perm = nullptr,       // perm [B][L][L] bytes or null: != 0 <=> query i may not attend to key j (xlnet.py:265-296)
-                            int gstream = 0);                    // 1: the query stream's mask (attn_mask_g = data_mask, no i == j exemption; xlnet.py:288-296)
+                            int gstream = 0,                     // 1: the query stream's mask (attn_mask_g = data_mask, no i == j exemption; xlnet.py:288-296)
+                            float* stats = nullptr);             // L > 128: xlnet_tiled_stats_floats(B, L, nh) floats
 int xlnet_attention_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
                              const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
                              const void* psave, const void* dvec, void* gsave, void* dqkv, void* dkr, float* d_rwb,
                              float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh, DropKey drop, hipStream_t st,
                              const float* head_scale = nullptr,      // head_scale [nh] or null: head_mask of the layer
                              GradAcc acc = {},                       // deterministic mode: the four bias / seg_embed column sums (common.h)
-                             const struct AdamRide* ride_q = nullptr, const struct AdamRide* ride_kv = nullptr);      // bf16, L <= 64: riders of the two launches
+                             const struct AdamRide* ride_q = nullptr, const struct AdamRide* ride_kv = nullptr,      // bf16, L <= 64: riders of the two launches
+                             const void* vec = nullptr, const float* stats = nullptr, void* pdsave = nullptr,        // L > 128 (see above)
+                             const uint8_t* perm = nullptr);
 int xlnet_attention_backward_free_slots(int dtype, int L, int nblk, int cus);
+// the tiled kernels at any 1 <= L <= 512: stats = two fp32 planes of B*nh*L rows (m | 1/l); gsave / pdsave = [B*nh][LP][LP] elements of the
+// activation dtype, LP = L rounded up to 64 (written by the backward's first launch, read by the other two).  The forward with
+// probs (fp32 [B][nh][L][L], the probabilities BEFORE dropout) may be given vec = stats = null: a pure recomputation.
+// MB_ERR_SHAPE when dropout is on and B*nh*L*L does not fit the uint32 mask index.
+size_t xlnet_tiled_stats_floats(int B, int L, int nh);
+size_t xlnet_tiled_scratch_elems(int B, int L, int nh);
+int xlnet_attention_tiled_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                  const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
+                                  float* stats, int B, int L, int nh, DropKey drop, hipStream_t st, const float* head_scale = nullptr,
+                                  const uint8_t* perm = nullptr, int gstream = 0, float* probs = nullptr);
+int xlnet_attention_tiled_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                   const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
+                                   const void* vec, const void* dvec, const float* stats, void* gsave, void* pdsave, void* dqkv, void* dkr,
+                                   float* d_rwb, float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh, DropKey drop,
+                                   hipStream_t st, const float* head_scale = nullptr, const uint8_t* perm = nullptr, GradAcc acc = {});
 // out[t] = dropout(word[ids[t]])  (xlnet.py:304-305) ; backward scatter-adds into dword
 int gather_drop_forward(int dtype, const int64_t* ids, const float* word, void* out, int rows, int H, DropKey drop, hipStream_t st);
 int gather_drop_backward(int dtype, const void* dout, const int64_t* ids, float* dword, int rows, int H, DropKey drop, hipStream_t st, GradAcc acc = {});

@@ -1,5 +1,6 @@
 // XLNet relative attention core (transformers 3.0.2 XLNetRelativeAttention.rel_attn_core, reached from
-// /root/reference/xlnet.py:374-385), forward and backward, L <= 128, head dim 64, one workgroup per (batch, head[, strip group]):
+// /root/reference/xlnet.py:374-385), forward and backward, L <= 128, head dim 64, one workgroup per (batch, head[, strip group])
+// (the host entries at the end of this file hand 128 < L <= 512 to the tiled kernels of xlnet_attention_tiled.hip):
 //     ac[i,j] = (q_i + r_w_bias) . k_j
 //     bd[i,j] = (q_i + r_r_bias) . kr_{L-i+j}          (rel_shift folded into the index: no [L,2L] reshape tricks)
 //     ef[i,j] = (q_i + r_s_bias) . seg_embed[seg_i != seg_j]
@@ -757,7 +758,11 @@ __global__ void __launch_bounds__(NW * 64) xl_attn_bwd_kv2_ride_kernel(const T* 
 int xlnet_attention_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
                             const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
                             void* psave, int B, int L, int nh, DropKey drop, hipStream_t st, const float* head_scale, const uint8_t* perm,
-                            int gstream) {
+                            int gstream, float* stats) {
+    // by L alone: the LDS-resident kernels up to 128 (psave), the tiled ones above (stats; no saved probabilities)
+    if (L > 128)
+        return xlnet_attention_tiled_forward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, vec, stats, B, L, nh, drop, st,
+                                             head_scale, perm, gstream, nullptr);
     XlParams xp = {r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, head_scale, perm, gstream, GradAcc{nullptr, nullptr}};
     XL_DISPATCH({
         (void)NWQ; (void)NWK;
@@ -781,7 +786,13 @@ int xlnet_attention_backward(int dtype, const void* qkv, const void* kr, const f
                              const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
                              const void* psave, const void* dvec, void* gsave, void* dqkv, void* dkr, float* d_rwb,
                              float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh, DropKey drop, hipStream_t st,
-                             const float* head_scale, GradAcc acc, const AdamRide* ride_q, const AdamRide* ride_kv) {
+                             const float* head_scale, GradAcc acc, const AdamRide* ride_q, const AdamRide* ride_kv, const void* vec,
+                             const float* stats, void* pdsave, const uint8_t* perm) {
+    if (L > 128) {          // the tiled kernels: psave unused; they recompute the scores (perm again) and take no riders
+        if ((ride_q != nullptr && ride_q->blocks > 0) || (ride_kv != nullptr && ride_kv->blocks > 0)) return MB_ERR_MODE;
+        return xlnet_attention_tiled_backward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, vec, dvec, stats, gsave, pdsave,
+                                              dqkv, dkr, d_rwb, d_rrb, d_rsb, d_seg, B, L, nh, drop, st, head_scale, perm, acc);
+    }
     static int g_kv2 = -1;            // MB_XL_KV2=0: the key / position side of the backward with the round-3 kernel at L <= 64 too (A/B)
     if (g_kv2 < 0) { const char* v = getenv("MB_XL_KV2"); g_kv2 = v ? atoi(v) : 1; }
     XlParams xp = {r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, head_scale, nullptr, 0, acc};

@@ -3,7 +3,8 @@
 // caller-owned flat parameter / gradient / bf16-shadow / workspace buffers, reference state-dict names.
 //
 // Only the configuration the reference driver exercises is built (xlnet-base-cased: attn_type "bi", no mems / perm_mask /
-// target_mapping; multimodal_driver.py:363-370), sequence length <= 128 (MOSI: 50).
+// target_mapping; multimodal_driver.py:363-370).  Sequence length: up to 128 the LDS-resident relative-attention kernels (MOSI: 50),
+// above it, up to 512, the tiled ones (xlnet_attention_tiled.hip) -- the dispatch is xlnet_attention_forward / _backward's, by L alone.
 //
 // Flat layout:  [ decay | no-decay | frozen ]
 //   decay    : per layer rel_attn.{q,k,v,o,r} ([d_model][n_head*d_head], consumed k-major as stored), ff.layer_1.weight,
@@ -18,7 +19,7 @@
 #include "comm.h"
 
 struct XlLayerOff { size_t q, k, v, o, r, w1, w2, seg, ralnw, fflnw, rrb, rsb, rwb, ralnb, fflnb, b1, b2; };
-struct XlLayerWs { size_t qkv, kr, vec, psave, s1, st1, y1, u, g, s2, st2; };
+struct XlLayerWs { size_t qkv, kr, vec, psave, s1, st1, y1, u, g, s2, st2, stats; };     // max_seq > 128: stats (tiled attention's rows) instead of psave
 
 struct mb_xlnet_engine : StepMixin {
     mb_xlnet_config c;
@@ -33,6 +34,10 @@ struct mb_xlnet_engine : StepMixin {
     std::vector<XlLayerWs> lw;
     size_t ws_dsa[2], ws_dzda[2], ws_dsb[2], ws_dzdb[2], ws_du[2], ws_dqkv[2], ws_dkr[2];   // dY operands of the weight gradients: ping-pong by layer parity
     size_t ws_dxa, ws_dxb, ws_dvec, ws_gsave, ws_dz, ws_dxs, ws_lnp_a, ws_lnp_b;
+    size_t ws_pdsave = 0;          // max_seq > 128: the tiled backward's second shared scratch plane (dropped probabilities)
+    bool tiled() const { return c.max_seq > 128; }
+    float* attn_stats(const XlLayerWs& w) const { return tiled() ? (float*)(ws + w.stats) : nullptr; }
+    char* attn_pdsave() const { return tiled() ? ws + ws_pdsave : nullptr; }
     size_t ws_rhalf = 0;           // fp32 [H][H]: the second k-half of a layer's relative-position weight gradient (see mb_xlnet_backward)
     int split_r = 1;               // MB_XL_SPLIT_R=0: the r problem of the grouped launch keeps its whole K = 2 x tokens (round-3 form)
     size_t lnp_stride = 0;         // floats per layer in each of the two LayerNorm partial buffers
@@ -147,7 +152,10 @@ static void xl_build_layout(mb_xlnet_engine* e) {
     const size_t T = align_up((size_t)c.max_batch * c.max_seq, 64);
     const size_t R = align_up((size_t)c.max_batch * 2 * c.max_seq, 64);
     const size_t LPm = c.max_seq <= 32 ? 32 : (c.max_seq <= 64 ? 64 : 128);
-    const size_t PP = (size_t)c.max_batch * nh * LPm * LPm;    // saved probabilities / score gradients: [B * heads][LP][LP], LP = 32 | 64 | 128
+    // saved probabilities / score gradients: [B * heads][LP][LP], LP = 32 | 64 | 128.  max_seq > 128 (tiled attention): the long passes save
+    // no probabilities -- per-layer row statistics instead, O(B * heads * L) floats -- and share TWO planes with LP = max_seq rounded up to 64
+    const bool tiled = c.max_seq > 128;
+    const size_t PP = tiled ? xlnet_tiled_scratch_elems(c.max_batch, c.max_seq, (int)nh) : (size_t)c.max_batch * nh * LPm * LPm;
     Carver w;
     e->mw.init(c.dtype, (int)T, (int)H, (int)V, (int)A);
     e->ws_mag = w.take(e->mw.bytes);
@@ -165,7 +173,15 @@ static void xl_build_layout(mb_xlnet_engine* e) {
     e->lw.resize(c.n_layer);
     for (int l = 0; l < c.n_layer; ++l) {
         XlLayerWs& x = e->lw[l];
-        x.qkv = w.take(T * 3 * H * es); x.kr = w.take(R * H * es); x.vec = w.take(T * H * es); x.psave = w.take(PP * es);
+        x.qkv = w.take(T * 3 * H * es); x.kr = w.take(R * H * es); x.vec = w.take(T * H * es);
+        if (!tiled) { x.psave = w.take(PP * es); x.stats = 0; }
+        else {
+            // (passes of L <= 128 on such an engine still run the LDS-resident kernels, bit for bit: they keep a 128-row psave --
+            //  max_batch * 12 heads * 128 * 128 elements per layer, 393 KB per sample and layer in bf16: 604 MB at max_batch = 128,
+            //  12 layers, which the long passes never touch)
+            x.psave = w.take((size_t)c.max_batch * nh * 128 * 128 * es);
+            x.stats = w.take(xlnet_tiled_stats_floats(c.max_batch, c.max_seq, (int)nh) * 4);
+        }
         x.s1 = w.take(T * H * es); x.st1 = w.take(2 * T * 4); x.y1 = w.take(T * H * es); x.u = w.take(T * I * es);
         x.g = w.take(T * I * es); x.s2 = w.take(T * H * es); x.st2 = w.take(2 * T * 4);
     }
@@ -179,6 +195,7 @@ static void xl_build_layout(mb_xlnet_engine* e) {
         e->ws_dkr[k] = w.take(R * H * es);
     }
     e->ws_dvec = w.take(T * H * es); e->ws_gsave = w.take(PP * es);
+    if (tiled) e->ws_pdsave = w.take(PP * es);
     e->ws_demb = w.take(T * H * 4);
     e->ws_dz = w.take((size_t)c.max_batch * H * es); e->ws_dxs = w.take((size_t)c.max_batch * H * es);
     e->ws_rhalf = w.take((size_t)H * H * 4);
@@ -225,7 +242,7 @@ extern "C" {
 int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out) {
     if (!cfg || !out) return MB_ERR_ARG;
     if (cfg->d_model != 768 || cfg->n_head * 64 != cfg->d_model) return MB_ERR_SHAPE;
-    if (cfg->d_inner % 128 || cfg->max_seq < 1 || cfg->max_seq > 128 || cfg->max_batch < 1 || cfg->num_labels < 1) return MB_ERR_SHAPE;
+    if (cfg->d_inner % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1 || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->injection_index < 0 || cfg->injection_index >= cfg->n_layer) return MB_ERR_ARG;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
     mb_xlnet_engine* e = new mb_xlnet_engine();
@@ -363,7 +380,7 @@ static int xl_forward_range(mb_xlnet_engine* e, const int64_t* input_ids, const 
         CK(gemm(dt, GEMM_NN, EPI_ADD_RES, R, H, H, ws + e->ws_pos, H, e->W(o.r), H, ws + w.kr, H, nullptr, nullptr, nullptr, nullptr, 0, kNoDrop, 1, 0, st));
         CK(xlnet_attention_forward(dt, qkv, ws + w.kr, P + o.rwb, P + o.rrb, P + o.rsb, P + o.seg, token_type_ids, attention_mask,
                                    ws + w.vec, ws + w.psave, B, L, nh, e->key(XS_LAYER0 + 8 * l + 0, pd), st,
-                                   e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, e->perm));
+                                   e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, e->perm, 0, e->attn_stats(w)));
         // post_attention: dropout(vec . o^T) + h -> LayerNorm
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, T, H, H, ws + w.vec, H, e->W(o.o), H, ws + w.s1, H, nullptr, nullptr, nullptr, xin, H,
                 e->key(XS_LAYER0 + 8 * l + 1, pd), 1, 0, st));
@@ -525,7 +542,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                                  e->ride_opts, e->cu_count(), take_l));
             // (riders of the two relative-attention backward launches: 576 workgroups in 768 slots each at L = 50, latency-bound hosts)
             AdamRide rq = {}, rkv = {};
-            if (riding && e->ride_attn) {
+            if (riding && e->ride_attn && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
                 int free_slots = xlnet_attention_backward_free_slots(dt, L, B * nh, e->cu_count());
                 if (e->ride_attn_blocks > 0 && free_slots > 0) free_slots = e->ride_attn_blocks;
                 const int blocks = std::min(free_slots, 2 * e->cu_count()) / 8 * 8;
@@ -544,7 +561,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                                         ws + w.psave, ws + e->ws_dvec, ws + e->ws_gsave, dqkv, dkr, G + o.rwb, G + o.rrb,
                                         G + o.rsb, G + o.seg, B, L, nh, e->key(XS_LAYER0 + 8 * l + 0, pd), st,
                                         e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, rq.blocks ? &rq : nullptr,
-                                        rkv.blocks ? &rkv : nullptr));
+                                        rkv.blocks ? &rkv : nullptr, ws + w.vec, e->attn_stats(w), e->attn_pdsave(), e->perm));
             if (grouped && e->deferred) {
                 if (!e->side) {
                     CK((int)hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
@@ -949,8 +966,19 @@ const void* mb_xlnet_hidden_state(const mb_xlnet_engine* e, int i) {      // inp
 }
 const void* mb_xlnet_attention_probs(const mb_xlnet_engine* e, int layer, int* padded_len) {
     if (!e || !e->ws || !e->ran_forward || layer < 0 || layer >= e->c.n_layer) return nullptr;
+    if (e->tiled()) return nullptr;          // no saved probabilities there: mb_xlnet_attention_probs_into recomputes them
     if (padded_len) *padded_len = e->L <= 32 ? 32 : (e->L <= 64 ? 64 : 128);
     return e->ws + e->lw[layer].psave;
+}
+int mb_xlnet_attention_probs_into(mb_xlnet_engine* e, int layer, float* out, void* stream) {
+    if (!e || !out) return MB_ERR_ARG;
+    if (!e->P || !e->ws || !e->ran_forward || layer < 0 || layer >= e->c.n_layer) return MB_ERR_ARG;
+    const mb_xlnet_config& c = e->c;
+    const XlLayerOff& o = e->lo[layer];
+    const XlLayerWs& w = e->lw[layer];
+    // a post-pass over what the last forward left of this layer (q | k | v, kr) and the pass's masks: the tiled forward's probability sweep
+    return xlnet_attention_tiled_forward(c.dtype, e->ws + w.qkv, e->ws + w.kr, e->P + o.rwb, e->P + o.rrb, e->P + o.rsb, e->P + o.seg, e->seg,
+                                         e->mask, nullptr, nullptr, e->B, e->L, c.n_head, kNoDrop, (hipStream_t)stream, nullptr, e->perm, 0, out);
 }
 const void* mb_xlnet_sequence_output(const mb_xlnet_engine* e) { return e->ws ? e->ws + e->ws_x[e->c.n_layer] : nullptr; }
 int mb_xlnet_set_inputs_embeds(mb_xlnet_engine* e, const float* inputs_embeds) {
@@ -979,6 +1007,57 @@ int mb_xlnet_backward_outputs(mb_xlnet_engine* e, const void* d_output, void* st
     CK(e->begin_backward_pass(e->G, st));
     const mb_xlnet_config& c = e->c;
     return drop_rows(c.dtype, d_output, e->ws + e->ws_dxa, e->B * e->L, c.d_model, e->key(XS_FINAL, c.dropout), st);
+}
+
+// ---------------------------------------------------------------------------------------------- relative attention at the operator level
+static int xl_op_check(int dtype, int B, int L, int nh) {
+    if (B < 1 || L < 1 || L > 512 || nh < 1) return MB_ERR_SHAPE;
+    if (dtype != DT_BF16 && dtype != DT_F32) return MB_ERR_DTYPE;
+    return MB_OK;
+}
+size_t mb_xlnet_attention_tiled_stats_bytes(int B, int L, int nh) {
+    return (B < 1 || L < 1 || nh < 1) ? 0 : xlnet_tiled_stats_floats(B, L, nh) * sizeof(float);
+}
+size_t mb_xlnet_attention_tiled_scratch_bytes(int dtype, int B, int L, int nh) {
+    return (B < 1 || L < 1 || nh < 1 || (dtype != DT_BF16 && dtype != DT_F32)) ? 0 : xlnet_tiled_scratch_elems(B, L, nh) * esize(dtype);
+}
+int mb_xlnet_attention_tiled_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                     const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
+                                     float* stats, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                                     const uint8_t* perm, int gstream, float* probs, void* stream) {
+    return xlnet_attention_tiled_forward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, vec, stats, B, L, nh, dk(drop),
+                                         (hipStream_t)stream, head_scale, perm, gstream, probs);
+}
+int mb_xlnet_attention_tiled_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                      const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
+                                      const void* vec, const void* dvec, const float* stats, void* gsave, void* pdsave, void* dqkv,
+                                      void* dkr, float* d_rwb, float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh,
+                                      const mb_dropkey* drop, const float* head_scale, const uint8_t* perm, void* stream) {
+    return xlnet_attention_tiled_backward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, vec, dvec, stats, gsave, pdsave,
+                                          dqkv, dkr, d_rwb, d_rrb, d_rsb, d_seg, B, L, nh, dk(drop), (hipStream_t)stream, head_scale, perm);
+}
+int mb_xlnet_attention_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                               const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
+                               void* psave, float* stats, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                               const uint8_t* perm, int gstream, void* stream) {
+    if (int e = xl_op_check(dtype, B, L, nh)) return e;
+    if (!qkv || !kr || !r_w_bias || !r_r_bias || !r_s_bias || !seg_embed || !seg || !mask || !vec) return MB_ERR_ARG;
+    if (L <= 128 ? !psave : !stats) return MB_ERR_ARG;      // the resident forward writes the probabilities, the tiled one the row statistics
+    return xlnet_attention_forward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, vec, psave, B, L, nh, dk(drop),
+                                   (hipStream_t)stream, head_scale, perm, gstream, stats);
+}
+int mb_xlnet_attention_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
+                                const void* psave, const void* vec, const void* dvec, const float* stats, void* gsave, void* pdsave,
+                                void* dqkv, void* dkr, float* d_rwb, float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh,
+                                const mb_dropkey* drop, const float* head_scale, const uint8_t* perm, void* stream) {
+    if (int e = xl_op_check(dtype, B, L, nh)) return e;
+    if (!qkv || !kr || !r_w_bias || !r_r_bias || !r_s_bias || !seg_embed || !seg || !mask || !dvec || !gsave || !dqkv || !dkr || !d_rwb ||
+        !d_rrb || !d_rsb || !d_seg || (L <= 128 && !psave))
+        return MB_ERR_ARG;
+    return xlnet_attention_backward(dtype, qkv, kr, r_w_bias, r_r_bias, r_s_bias, seg_embed, seg, mask, psave, dvec, gsave, dqkv, dkr, d_rwb,
+                                    d_rrb, d_rsb, d_seg, B, L, nh, dk(drop), (hipStream_t)stream, head_scale, GradAcc{}, nullptr, nullptr, vec,
+                                    stats, pdsave, perm);
 }
 
 int mb_xlnet_stage_grad_ranges(const mb_xlnet_engine* e, int stage, size_t* offs, size_t* lens, int cap) {

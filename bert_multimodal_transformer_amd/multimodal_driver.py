@@ -378,10 +378,10 @@ def prep_for_training(num_train_optimization_steps: int):
         if args.pretrained:
             model = MAG_XLNetForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt)
+                compute_dtype=dt, max_seq_length=args.max_seq_length)
         else:
             model = MAG_XLNetForSequenceClassification(XLNetConfig(num_labels=1), multimodal_config, visual_dim=V,
-                                                       acoustic_dim=A, compute_dtype=dt)
+                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     model.to(_device())
     optimizer = AdamW(optimizer_grouped_parameters(model), lr=args.learning_rate)
     scheduler = get_linear_schedule_with_warmup(

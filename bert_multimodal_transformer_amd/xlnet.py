@@ -1,5 +1,5 @@
 """MAG_XLNetModel / MAG_XLNetForSequenceClassification -- drop-in surfaces of /root/reference/xlnet.py:15-527 on the native
-MI355X step executor (csrc/xlnet_engine.hip, csrc/xlnet_attention.hip).
+MI355X step executor (csrc/xlnet_engine.hip, csrc/xlnet_attention.hip, csrc/xlnet_attention_tiled.hip).
 
 Same class names, constructor `(config, multimodal_config)`, forward argument order and state-dict keys as the reference
 (transformer.word_embedding.weight, transformer.mask_emb, transformer.layer.{i}.rel_attn.{q,k,v,o,r,r_r_bias,r_s_bias,
@@ -10,8 +10,9 @@ adjoint); mems (forward and backward of MAG_XLNetForSequenceClassification; the 
 (config.mem_len, use_cache); target_mapping (the query stream g, xlnet.py:306-313, 374-399) for inference -- eval mode under
 torch.no_grad(), without mems / output_attentions; inputs_embeds, output_hidden_states / output_attentions (served from the activations the engine keeps for
 its backward) and head_mask (scales each head's attention output inside the kernels) are built, and MAG_XLNetModel's output is
-differentiable), sequence length <= 128, MAG injected in front of layer
-XLNET_INJECTION_INDEX (global_configs.py:19, xlnet.py:371-372).
+differentiable), MAG injected in front of layer XLNET_INJECTION_INDEX (global_configs.py:19, xlnet.py:371-372).
+Sequence length: `max_seq_length=None` (or <= 128) keeps the limit of 128 rows of the LDS-resident relative-attention kernels;
+up to 512 the engine runs the tiled kernels for the passes that are longer than 128 (with mems the limit is on klen = mlen + seq_len).
 """
 import torch
 import torch.nn as nn
@@ -61,12 +62,13 @@ class MAG_XLNetModel(_XlBase):
     """xlnet.py:15-429.  forward -> (output [B, L, d_model],) as an fp32 copy of the engine activation."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None, injection_index=XLNET_INJECTION_INDEX, _core=None):
+                 compute_dtype=torch.float32, device=None, injection_index=XLNET_INJECTION_INDEX, _core=None, max_seq_length=None):
+        """max_seq_length: the longest sequence (with mems: klen) this instance will run -- None or <= 128: 128, at most 512."""
         super().__init__()
         self.config = config
         own = _core is None
         self._core = _core or _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, kind="xlnet",
-                                    injection_index=injection_index)
+                                    injection_index=injection_index, max_seq_length=max_seq_length)
         _attach_parameters(self, self._core, prefix_filter="transformer.", strip="transformer.")
         if own:
             self.init_weights()
@@ -130,8 +132,8 @@ def _xl_mems_front(model, mems, input_ids, inputs_embeds, visual, acoustic, atte
     mlen, H, dev = int(mems[0].shape[0]), core.config.d_model, core.device
     if any(tuple(m.shape) != (mlen, B, H) for m in mems):
         raise ValueError("every element of mems must be [mlen, batch, d_model] = %s" % ((mlen, B, H),))
-    if mlen + L > 128:
-        raise NotImplementedError("klen = mlen + seq_len = %d exceeds the 128 rows the relative-attention kernels hold" % (mlen + L))
+    if mlen + L > core.max_seq_length:
+        raise NotImplementedError("klen = mlen + seq_len = %d exceeds this model's max_seq_length = %d rows" % (mlen + L, core.max_seq_length))
     stack = torch.stack([m.detach().to(dev, torch.float32).permute(1, 0, 2) for m in mems]).to(core.compute_dtype).contiguous()
     pad = lambda t, fill, dt: torch.cat([torch.full((B, mlen) + tuple(t.shape[2:]), fill, dtype=dt, device=dev), t.to(dev, dt)], dim=1)
     if input_ids is not None:
@@ -215,12 +217,13 @@ class MAG_XLNetForSequenceClassification(_FusedStep, _XlBase):
     """xlnet.py:432-527."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None, injection_index=XLNET_INJECTION_INDEX):
+                 compute_dtype=torch.float32, device=None, injection_index=XLNET_INJECTION_INDEX, max_seq_length=None):
+        """max_seq_length: as MAG_XLNetModel's."""
         super().__init__()
         self.config = config
         self.num_labels = config.num_labels
         self._core = _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, kind="xlnet",
-                           injection_index=injection_index)
+                           injection_index=injection_index, max_seq_length=max_seq_length)
         self.transformer = MAG_XLNetModel(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device,
                                           injection_index, _core=self._core)
         _attach_parameters(self, self._core, prefix_filter="sequence_summary.")

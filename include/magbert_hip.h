@@ -285,7 +285,12 @@ int mb_bert_profile_adamw_us(mb_bert_engine* e, float* us);
 
 /* ------------------------------------------------------------------------------------------------ MAG-XLNet engine
  * MAG_XLNetForSequenceClassification forward / backward (xlnet.py:432-527 -> :15-429; XLNetLayer / SequenceSummary of
- * transformers 3.0.2) for the driver's configuration (bi-directional, no mems / perm_mask / target_mapping), L <= 128.
+ * transformers 3.0.2) for the driver's configuration (bi-directional, no mems / perm_mask / target_mapping).  max_seq may be
+ * anything up to 512 (XLNet has no position table; 512 is the kernels' limit): passes with L <= 128 run the LDS-resident
+ * relative-attention kernels, longer ones the tiled kernels (mb_xlnet_attention_tiled_* below), whatever max_seq is.  An engine
+ * with max_seq <= 128 carves the workspace it always carved; above it the per-layer saved probabilities stay at 128 rows (for the
+ * short passes), the long passes keep per-layer row statistics instead and share two [B * n_head][LP][LP] planes (LP = max_seq
+ * rounded up to 64).
  * Same calling conventions as the mb_bert_* family.  Backward stages: 0 = summary + logits_proj, 1..n_layer = layers (last
  * first; the MAG backward runs inside the stage of layer `injection_index`), n_layer+1 = word embedding. */
 typedef struct {
@@ -298,6 +303,44 @@ typedef struct {
 } mb_xlnet_config;
 
 typedef struct mb_xlnet_engine mb_xlnet_engine;
+
+/* XLNet's relative attention core at the operator level (dh = 64; transformers 3.0.2 rel_attn_core):
+ *     S[i,j] = ((q_i + r_w_bias) . k_j + (q_i + r_r_bias) . kr[b][L - i + j] + (q_i + r_s_bias) . seg_embed[seg_i != seg_j]) / 8
+ *              - 1e30 * [(mask[b][j] == 0 or perm[b][i][j]) and (i != j or gstream)]
+ *     vec_i  = head_scale[h] * sum_j dropout(softmax_j S)[i,j] v_j
+ * qkv [B*L][3H] token-major (q | k | v), kr [B][2L][H], r_*_bias fp32 [nh][64], seg_embed fp32 [2][nh][64], seg / mask int64 [B][L],
+ * perm bytes [B][L][L] or NULL, head_scale fp32 [nh] or NULL, vec / dvec [B*L][H]; the backward writes dqkv [B*L][3H], dkr [B][2L][H]
+ * and ADDS the four parameter gradients into d_rwb / d_rrb / d_rsb [nh][64] and d_seg [2][nh][64].  gstream = 1 (the query stream's
+ * mask) exists in the forward only.  Dropout: counter hash, element index ((b*nh + h)*L + i)*L + j.
+ * mb_xlnet_attention_tiled_*: the kernels the engine runs for 128 < L <= 512, usable at any 1 <= L <= 512.  stats: caller scratch of
+ * mb_xlnet_attention_tiled_stats_bytes(B, L, nh), written by the forward (row maxima and 1/normalisers), read by the backward together
+ * with the forward's vec.  gsave / pdsave: two caller scratch planes of mb_xlnet_attention_tiled_scratch_bytes(dtype, B, L, nh) each.
+ * probs (fp32 [B][nh][L][L] or NULL): the probabilities before dropout; with probs the forward accepts vec = stats = NULL.
+ * Every dq / dk / dv / dkr element has one writer: reruns are bit-identical.  MB_ERR_SHAPE (1001) for L outside [1, 512] and when
+ * dropout is on and B*nh*L*L >= 2^32; shapes are checked before any pointer is looked at.
+ * mb_xlnet_attention_forward / _backward: the engine's dispatch -- L <= 128 the LDS-resident kernels (psave / gsave
+ * [B*nh][LP][LP] in the activation dtype, LP = 32 | 64 | 128 >= L: the forward saves the probabilities, the backward reads them;
+ * vec / stats / pdsave / perm of the backward unused), above it the tiled ones (psave unused). */
+size_t mb_xlnet_attention_tiled_stats_bytes(int B, int L, int nh);
+size_t mb_xlnet_attention_tiled_scratch_bytes(int dtype, int B, int L, int nh);
+int mb_xlnet_attention_tiled_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                     const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
+                                     float* stats, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                                     const uint8_t* perm, int gstream, float* probs, void* stream);
+int mb_xlnet_attention_tiled_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                      const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
+                                      const void* vec, const void* dvec, const float* stats, void* gsave, void* pdsave, void* dqkv,
+                                      void* dkr, float* d_rwb, float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh,
+                                      const mb_dropkey* drop, const float* head_scale, const uint8_t* perm, void* stream);
+int mb_xlnet_attention_forward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                               const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask, void* vec,
+                               void* psave, float* stats, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
+                               const uint8_t* perm, int gstream, void* stream);
+int mb_xlnet_attention_backward(int dtype, const void* qkv, const void* kr, const float* r_w_bias, const float* r_r_bias,
+                                const float* r_s_bias, const float* seg_embed, const int64_t* seg, const int64_t* mask,
+                                const void* psave, const void* vec, const void* dvec, const float* stats, void* gsave, void* pdsave,
+                                void* dqkv, void* dkr, float* d_rwb, float* d_rrb, float* d_rsb, float* d_seg, int B, int L, int nh,
+                                const mb_dropkey* drop, const float* head_scale, const uint8_t* perm, void* stream);
 
 int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out);
 void mb_xlnet_destroy(mb_xlnet_engine* e);
@@ -325,6 +368,11 @@ const void* mb_xlnet_hidden_state(const mb_xlnet_engine* e, int i);
  * attention dropout (the host multiplies the counter-hash mask of site XS_LAYER0 + 8 * layer in train mode).  Valid until the
  * next forward. */
 const void* mb_xlnet_attention_probs(const mb_xlnet_engine* e, int layer, int* padded_len);
+/* The same for engines with max_seq > 128, which save no probabilities (mb_xlnet_attention_probs returns NULL there): a post-pass over
+ * what the last forward left of layer `layer` (q | k | v, kr) and that pass's attention_mask / token_type_ids / perm_mask, which must
+ * still be alive.  out: fp32 [B][n_head][L][L], device -- the probabilities BEFORE the attention dropout and the head mask, as above.
+ * Works for every engine and length; valid until the next forward. */
+int mb_xlnet_attention_probs_into(mb_xlnet_engine* e, int layer, float* out, void* stream);
 /* head_mask (xlnet.py:340-353, 383): fp32 [n_layer][n_head] device memory, sticky until reset with NULL; head h of layer l
  * contributes head_mask[l][h] times its attention output (attn_prob * head_mask after the dropout).  Explicit forwards /
  * backwards only: mb_xlnet_train_step returns MB_ERR_MODE while it is set. */
