@@ -28,15 +28,59 @@ from . import _lib
 from .global_configs import ACOUSTIC_DIM, VISUAL_DIM
 
 
+SUPPORTED_HIDDEN_SIZES = (256, 512, 768, 1024)      # what the row kernels, MAG and the head are instantiated for (heads of 64)
+
+
+def check_bert_sizes(config):
+    """The model sizes the MAG-BERT engine runs: hidden_size in SUPPORTED_HIDDEN_SIZES with heads of 64 (the compact BERTs 256 / 4 and
+    512 / 8, bert-base 768 / 12, bert-large 1024 / 16), any depth, intermediate_size a multiple of 128.  Raises ValueError otherwise."""
+    H, nh, I, NL = (int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size), int(config.num_hidden_layers))
+    if H not in SUPPORTED_HIDDEN_SIZES:
+        raise ValueError("hidden_size = %d: the HIP engine runs hidden sizes %s (heads of 64)" % (H, ", ".join(map(str, SUPPORTED_HIDDEN_SIZES))))
+    if nh * 64 != H:
+        raise ValueError("num_attention_heads = %d with hidden_size = %d: the attention kernels take heads of 64 (%d heads); hidden sizes %s"
+                         % (nh, H, H // 64, ", ".join(map(str, SUPPORTED_HIDDEN_SIZES))))
+    if I % 128 or I < 128:
+        raise ValueError("intermediate_size = %d: must be a multiple of 128" % I)
+    if NL < 1:
+        raise ValueError("num_hidden_layers = %d: at least one layer" % NL)
+
+
 class BertConfig(object):
-    """The subset of transformers.BertConfig the path reads (bert-base-uncased defaults)."""
+    """The subset of transformers.BertConfig the path reads (bert-base-uncased defaults).
+
+    Sizes the engine runs (check_bert_sizes, applied when a model is constructed): hidden_size 256, 512, 768 or 1024 with
+    num_attention_heads = hidden_size / 64, any num_hidden_layers >= 1, intermediate_size a multiple of 128 -- e.g.
+    bert-large-uncased is BertConfig.large(): hidden_size=1024, num_attention_heads=16, num_hidden_layers=24, intermediate_size=4096.
+    global_configs.TEXT_DIM is only the default width; the model takes its width from the config."""
+
+    KEYS = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "hidden_act",
+            "hidden_dropout_prob", "attention_probs_dropout_prob", "max_position_embeddings", "type_vocab_size", "initializer_range",
+            "layer_norm_eps", "pad_token_id")
+
+    @classmethod
+    def large(cls, **kwargs):
+        """bert-large-uncased: 24 layers x 1024 wide, 16 heads, 4096 intermediate (335 M parameters)"""
+        kw = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096)
+        kw.update(kwargs)
+        return cls(**kw)
+
+    @classmethod
+    def from_json_file(cls, path, **kwargs):
+        """A HuggingFace `config.json`: only the keys this class knows (KEYS) are read, everything else in the file is ignored."""
+        import json
+        with open(path) as f:
+            d = json.load(f)
+        kw = {k: d[k] for k in cls.KEYS if k in d}
+        kw.update(kwargs)
+        return cls(**kw)
 
     def __init__(self, vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12,
                  intermediate_size=3072, hidden_act="gelu", hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1,
                  max_position_embeddings=512, type_vocab_size=2, initializer_range=0.02, layer_norm_eps=1e-12,
                  pad_token_id=0, num_labels=1, **kwargs):
         if hidden_act != "gelu":
-            raise NotImplementedError("only erf-GELU (bert-base-uncased) is built")
+            raise NotImplementedError("only erf-GELU (hidden_act = \"gelu\", what the published BERT checkpoints use) is built")
         self.vocab_size = vocab_size
         self.hidden_size = hidden_size
         self.num_hidden_layers = num_hidden_layers
@@ -137,6 +181,8 @@ class _Core(object):
     def __init__(self, config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, kind="bert",
                  injection_index=1, max_seq_length=None):
         self.kind = kind                     # "bert" (mb_bert_*) or "xlnet" (mb_xlnet_*)
+        if kind == "bert":
+            check_bert_sizes(config)         # a clear message instead of the engine's "unsupported shape"
         self.injection_index = injection_index
         # the longest sequence this instance runs (both models) -- None or <= 128 keeps the limit of 128, above it the engine's attention
         # runs the tiled kernels (up to the position table; MAG-XLNet, which has no table: up to the kernels' 512)
@@ -787,6 +833,13 @@ def load_pretrained_state_dict(model, state_dict, base_prefix, source="checkpoin
     return {"missing_keys": missing, "unexpected_keys": unexpected, "error_msgs": []}
 
 
+def read_config_beside(path, num_labels=1):
+    """BertConfig from the `config.json` in the checkpoint directory `path` (or next to the checkpoint file `path`); None if there is none"""
+    d = path if os.path.isdir(path) else os.path.dirname(os.path.abspath(path))
+    j = os.path.join(d, "config.json")
+    return BertConfig.from_json_file(j, num_labels=num_labels) if os.path.isfile(j) else None
+
+
 def _pretrained_file(path, cls_name):
     if os.path.isdir(path):
         path = os.path.join(path, "pytorch_model.bin")
@@ -910,7 +963,9 @@ class _MagBertBase(nn.Module):
         multimodal_config = kwargs.pop("multimodal_config", model_args[0] if model_args else None)
         num_labels = kwargs.pop("num_labels", 1)
         want_info = kwargs.pop("output_loading_info", False)
-        config = config or cls._default_config(num_labels)
+        # no config given: the `config.json` next to the checkpoint says which model it is (a bert-large directory loads as
+        # bert-large); without one it is bert-base-uncased, as before
+        config = config or cls._config_beside(pretrained_model_name_or_path, num_labels) or cls._default_config(num_labels)
         config.num_labels = num_labels
         model = cls(config, multimodal_config, **kwargs)
         path = _pretrained_file(pretrained_model_name_or_path, cls.__name__)
@@ -921,6 +976,11 @@ class _MagBertBase(nn.Module):
     @staticmethod
     def _default_config(num_labels):
         return BertConfig(num_labels=num_labels)
+
+    @classmethod
+    def _config_beside(cls, path, num_labels):
+        # (MAG-BERT only: the MAG-XLNet classes share this from_pretrained and keep their default configuration)
+        return read_config_beside(path, num_labels) if cls.base_model_prefix == "bert" else None
 
 
 class _FusedStep(object):

@@ -377,8 +377,11 @@ std::vector<int> dp_chunk_plan(int n_layer) {
         const int c = atoi(v);
         if (c > 0 && c <= n_layer && n_layer % c == 0) { plan.assign((size_t)(n_layer / c), c); return plan; }
     }
+    // (12 layers: 4 | 4 | 2 | 2; 24: five pieces of 4, then 2 | 2; 6: 2 | 2 | 2.  Deeper than 48 layers the big pieces grow so that a step
+    //  never has more than 14 -- the comm object's event rings hold 16)
+    const int big = std::max(4, (n_layer + 11) / 12);
     int left = n_layer;
-    while (left > 4 && left - 4 >= 4) { plan.push_back(4); left -= 4; }
+    while (left > big && left - big >= 4) { plan.push_back(big); left -= big; }
     while (left > 2) { plan.push_back(2); left -= 2; }
     if (left > 0) plan.push_back(left);
     return plan;

@@ -382,7 +382,7 @@ int mb_mag_forward(int dtype, const void* text, const float* visual, const float
                    const float* b_hv, const float* W_ha, const float* b_ha, const float* W_v, const float* b_v,
                    const float* W_a, const float* b_a, const float* ln_w, const float* ln_b, float beta_shift,
                    const mb_dropkey* drop, void* out, void* ws, int T, int H, int V, int A, void* stream) {
-    if (H % 256 || H < 256 || H > 1024 || V < 1 || A < 1) return MB_ERR_SHAPE;      // the operator; the engines are built for 768
+    if (H % 256 || H < 256 || H > 1024 || V < 1 || A < 1) return MB_ERR_SHAPE;
     MagWs w;
     w.init(dtype, T, H, V, A);
     return mag_fwd_impl(dtype, text, visual, acoustic, W_hv, b_hv, W_ha, b_ha, W_v, b_v, W_a, b_a, ln_w, ln_b, 1e-5f,
@@ -417,7 +417,9 @@ int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n
 // ------------------------------------------------------------------------------------------------ engine API
 int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (!cfg || !out) return MB_ERR_ARG;
-    if (cfg->hidden_size != 768 || cfg->num_heads * 64 != cfg->hidden_size) return MB_ERR_SHAPE;
+    // hidden sizes 256 | 512 | 768 | 1024 (what the row kernels, MAG and the head are instantiated for), heads of 64, any depth >= 1
+    const int Hc = cfg->hidden_size;
+    if ((Hc != 256 && Hc != 512 && Hc != 768 && Hc != 1024) || cfg->num_heads * 64 != Hc || cfg->num_layers < 1) return MB_ERR_SHAPE;
     // max_seq > 128: the tiled attention kernels (up to 512 = BERT's position table)
     if (cfg->intermediate_size % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1) return MB_ERR_SHAPE;
     if (cfg->max_seq > cfg->max_position || cfg->num_labels < 1) return MB_ERR_SHAPE;
@@ -740,7 +742,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             AdamRide ra = {};
             if (e->ride_attn && inl && e->ride_m && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
                 int free_slots = attention_backward_free_slots(dt, L, B * nh, e->cu_count());
-                if (e->ride_attn_blocks > 0) free_slots = e->ride_attn_blocks;
+                if (e->ride_attn_blocks > 0 && free_slots > 0) free_slots = e->ride_attn_blocks;      // (fp32 has no rider kernel: 0 stays 0, or the slice a rider took would be skipped)
                 const int blocks = std::min(free_slots, 2 * e->cu_count()) / 8 * 8;
                 if (blocks >= 8) {
                     // L = 128: 128 whole CUs for about half the launch (~41 GB/s each): 20,480 parameters per rider workgroup -- same box, B = 32:
@@ -1127,9 +1129,10 @@ int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const flo
     e->training = 1;
     CK(prepare_pass(e, B * L, st));
     // (the plan is part of the graphs' identity: nseg alone would not tell 4,4,2,2 from 2,2,4,4)
-    int variant = 1;
-    for (int x : plan) variant = variant * 13 + x;
-    variant = (variant * 4 + comm->event_mode) * 2 + (comm->shard ? 1 : 0);
+    unsigned vh = 1;                                   // (unsigned: deep models have many pieces, the hash may wrap)
+    for (int x : plan) vh = vh * 13u + (unsigned)x;
+    vh = (vh * 4u + (unsigned)comm->event_mode) * 2u + (comm->shard ? 1u : 0u);
+    const int variant = (int)(vh & 0x7fffffffu) | 1;   // never 0, the single-process step's
     return train_step_impl(e, e->ws, c.visual_dim, c.acoustic_dim, c.num_labels, input_ids, visual, acoustic, attention_mask, token_type_ids,
                            labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2, eps, weight_decay, opt_step,
                            correct_bias, grad_scale, loss_scale, mode, e->prof, st,

@@ -751,8 +751,8 @@ static int tile_n768() {
 static int pn_cfg(const GemmArgs& a, bool ak, bool bk, int splits, bool forced, GemmArgs& p, int* tall = nullptr) {
     const int want = tall ? *tall : 0;
     if (tall) *tall = 0;
-    static int pn_max = -1, pt_on = -1;         // MB_GEMM_PN_MAX (measurement switch): the largest padded tile count the auto selection takes
-    if (pn_max < 0) { pn_max = env_int("MB_GEMM_PN_MAX", 256); pt_on = env_int("MB_GEMM_PT", 1); }
+    static int pn_max = -1, pn_min = 168, pt_on = -1;         // MB_GEMM_PN_MAX / _MIN (measurement switches): the largest / smallest padded tile count the auto selection takes
+    if (pn_max < 0) { pn_max = env_int("MB_GEMM_PN_MAX", 256); pn_min = env_int("MB_GEMM_PN_MIN", 168); pt_on = env_int("MB_GEMM_PT", 1); }
     if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
     const bool common = splits <= 1 && g_impl != 1 && g_stages <= 0 && a.bseg <= 0 && (a.lda % 8 == 0) && (a.ldb % 8 == 0) &&
                         (((uintptr_t)a.A | (uintptr_t)a.B) % 16 == 0) && (!bk || a.N % 64 == 0);
@@ -762,7 +762,7 @@ static int pn_cfg(const GemmArgs& a, bool ak, bool bk, int splits, bool forced, 
         p = a;
         const int tiles = form ? choose_regions<256, 64>(p) : choose_regions<128, 64>(p);
         const int ke = form ? 64 : 128, bm = form ? 256 : 128;
-        bool ok = (p.K % ke == 0) && p.K / ke >= 3 && (forced || (tiles <= pn_max && tiles >= 168));
+        bool ok = (p.K % ke == 0) && p.K / ke >= 3 && (forced || (tiles <= pn_max && tiles >= pn_min));
         if (ak) ok = ok && (p.M % bm == 0);
         if (!ok) continue;
         p.kchunk = p.K;

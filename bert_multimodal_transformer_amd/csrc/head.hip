@@ -4,7 +4,7 @@
 //   loss = mean((logits - labels)^2)                                  num_labels == 1 (the driver's regression)
 //   loss = mean_b(logsumexp(logits_b) - logits_b[label_b])            num_labels  > 1 (bert.py:318-320 / xlnet.py:519-522:
 //          CrossEntropyLoss; labels[b] then holds the class index of sample b as a float)
-// One wave per sample; H = 768 (3 chunks of 4 columns per lane).  Tiny, launch-latency bound.
+// One wave per sample; H = 256 * CH (CH chunks of 4 columns per lane: CH = 3 is bert-base, 4 bert-large).  Tiny, launch-latency bound.
 #include <algorithm>
 #include "kernels.h"
 
@@ -155,30 +155,32 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__
 
 int head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits,
                  float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st) {
-    if (H != 768) return MB_ERR_SHAPE;
+    if (H != 256 && H != 512 && H != 768 && H != 1024) return MB_ERR_SHAPE;
     if (B <= 0) return MB_OK;
-    hipLaunchKernelGGL((head_fwd_kernel<3>), dim3((B + 3) / 4), dim3(256), 0, st, z, Wc, bc, labels, pooled, logits, loss,
-                       loss_run, B, nl, drop);
+#define MB_HEAD_FWD(CH) hipLaunchKernelGGL((head_fwd_kernel<CH>), dim3((B + 3) / 4), dim3(256), 0, st, z, Wc, bc, labels, pooled, logits, loss, \
+                                           loss_run, B, nl, drop)
+    switch (H / 256) { case 1: MB_HEAD_FWD(1); break; case 2: MB_HEAD_FWD(2); break; case 3: MB_HEAD_FWD(3); break; default: MB_HEAD_FWD(4); break; }
+#undef MB_HEAD_FWD
     return (int)hipGetLastError();
 }
 
 int head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale,
                   const float* pooled, const float* Wc, void* dz, float* dWc, float* dbc, int B, int H, int nl,
                   DropKey drop, hipStream_t st, GradAcc acc, float* dbp, void* zero_p, size_t zero_bytes) {
-    if (H != 768) return MB_ERR_SHAPE;
+    if (H != 256 && H != 512 && H != 768 && H != 1024) return MB_ERR_SHAPE;
     if (B <= 0) return MB_OK;
     if (!dlogits && !(logits && labels)) return MB_ERR_ARG;
     if (zero_bytes % 16 || ((uintptr_t)zero_p & 15)) return MB_ERR_SHAPE;
     const int nb = (B + 3) / 4;
     const size_t n16 = zero_p ? zero_bytes / 16 : 0;
     const int zb = n16 ? (int)std::min<size_t>((n16 + 1023) / 1024, 512) : 0;
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL((head_bwd_kernel<bf16, 3>), dim3(nb + zb), dim3(256), 0, st, dlogits, logits, labels,
-                           loss_scale, pooled, Wc, (bf16*)dz, dWc, dbc, B, nl, drop, acc, dbp, (u32x4*)zero_p, n16, nb);
-    else if (dtype == DT_F32)
-        hipLaunchKernelGGL((head_bwd_kernel<float, 3>), dim3(nb + zb), dim3(256), 0, st, dlogits, logits, labels,
-                           loss_scale, pooled, Wc, (float*)dz, dWc, dbc, B, nl, drop, acc, dbp, (u32x4*)zero_p, n16, nb);
-    else return MB_ERR_DTYPE;
+    if (dtype != DT_BF16 && dtype != DT_F32) return MB_ERR_DTYPE;
+#define MB_HEAD_BWD(T, CH) hipLaunchKernelGGL((head_bwd_kernel<T, CH>), dim3(nb + zb), dim3(256), 0, st, dlogits, logits, labels, loss_scale, \
+                                              pooled, Wc, (T*)dz, dWc, dbc, B, nl, drop, acc, dbp, (u32x4*)zero_p, n16, nb)
+#define MB_HEAD_BWD_CH(CH) do { if (dtype == DT_BF16) MB_HEAD_BWD(bf16, CH); else MB_HEAD_BWD(float, CH); } while (0)
+    switch (H / 256) { case 1: MB_HEAD_BWD_CH(1); break; case 2: MB_HEAD_BWD_CH(2); break; case 3: MB_HEAD_BWD_CH(3); break; default: MB_HEAD_BWD_CH(4); break; }
+#undef MB_HEAD_BWD_CH
+#undef MB_HEAD_BWD
     return (int)hipGetLastError();
 }
 

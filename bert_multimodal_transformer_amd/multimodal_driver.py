@@ -69,6 +69,14 @@ def seed(s):
     raise argparse.ArgumentTypeError("Seed must be between 0 and 9999. Received {0}".format(s))
 
 
+BERT_MODELS = ("bert-base-uncased", "bert-large-uncased")      # everything that takes prepare_bert_input and the MAG-BERT classes
+
+
+def bert_config(model, num_labels=1):
+    """the configuration a --model name stands for (the checkpoint name is all the reference needs besides TEXT_DIM)"""
+    return BertConfig.large(num_labels=num_labels) if model == "bert-large-uncased" else BertConfig(num_labels=num_labels)
+
+
 def get_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--dataset", type=str, choices=["mosi", "mosei"], default="mosi")
@@ -79,7 +87,8 @@ def get_parser():
     parser.add_argument("--n_epochs", type=int, default=40)
     parser.add_argument("--beta_shift", type=float, default=1.0)
     parser.add_argument("--dropout_prob", type=float, default=0.5)
-    parser.add_argument("--model", type=str, choices=["bert-base-uncased", "xlnet-base-cased"], default="bert-base-uncased")
+    parser.add_argument("--model", type=str, choices=["bert-base-uncased", "bert-large-uncased", "xlnet-base-cased"],
+                        default="bert-base-uncased")
     parser.add_argument("--learning_rate", type=float, default=1e-5)
     parser.add_argument("--gradient_accumulation_step", type=int, default=1)
     parser.add_argument("--warmup_proportion", type=float, default=0.1)
@@ -142,7 +151,8 @@ def convert_to_features(examples, max_seq_length, tokenizer):
     """Feature conversion with the semantics of multimodal_driver.py:82-140: every wordpiece inherits the visual / acoustic
     row of the word it belongs to (a gather by owner index), the sequence is cut to max_seq_length - 2 pieces, and the
     model-specific layout (special tokens, padding side, segment ids) is applied by prepare_bert_input / prepare_xlnet_input."""
-    layout = {"bert-base-uncased": prepare_bert_input, "xlnet-base-cased": prepare_xlnet_input}[args.model]
+    layout = {"bert-base-uncased": prepare_bert_input, "bert-large-uncased": prepare_bert_input,
+              "xlnet-base-cased": prepare_xlnet_input}[args.model]
     room = max_seq_length - 2
     out = []
     for (words, visual, acoustic), label_id, _segment in examples:
@@ -194,11 +204,11 @@ def get_tokenizer(model):
         from transformers import BertTokenizer, XLNetTokenizer
     except Exception as e:      # pragma: no cover
         raise RuntimeError("transformers tokenizers unavailable: %s" % e)
-    if model == "bert-base-uncased":
+    if model in BERT_MODELS:
         return BertTokenizer.from_pretrained(model)
     elif model == "xlnet-base-cased":
         return XLNetTokenizer.from_pretrained(model)
-    raise ValueError("Expected 'bert-base-uncased' or 'xlnet-base-cased, but received {}".format(model))
+    raise ValueError("Expected 'bert-base-uncased', 'bert-large-uncased' or 'xlnet-base-cased, but received {}".format(model))
 
 
 def features_to_dataset(features):
@@ -365,13 +375,16 @@ def prep_for_training(num_train_optimization_steps: int):
     multimodal_config = MultimodalConfig(beta_shift=args.beta_shift, dropout_prob=args.dropout_prob)
     V, A = _dims()
     dt = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
-    if args.model == "bert-base-uncased":
+    if args.model in BERT_MODELS:
         if args.pretrained:
+            # (the checkpoint directory's config.json names the model size; without one: this --model's configuration)
+            from .bert import read_config_beside
             model = MAG_BertForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt, max_seq_length=args.max_seq_length)
+                compute_dtype=dt, max_seq_length=args.max_seq_length,
+                config=read_config_beside(args.pretrained, 1) or bert_config(args.model))
         else:       # offline: fresh init by the reference's init law
-            model = MAG_BertForSequenceClassification(BertConfig(num_labels=1), multimodal_config, visual_dim=V,
+            model = MAG_BertForSequenceClassification(bert_config(args.model), multimodal_config, visual_dim=V,
                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     elif args.model == "xlnet-base-cased":
         from .xlnet import MAG_XLNetForSequenceClassification, XLNetConfig

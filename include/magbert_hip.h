@@ -9,7 +9,8 @@
  *
  * dtype: 0 = fp32 "parity mode" (exact-fp32 MFMA, logits within 1e-3 of the CPU reference),
  *        1 = bf16 "perf mode" (bf16 activations / MFMA operands, fp32 accumulate, fp32 master weights).
- * All row-major.  T = B*L tokens, H = 768, heads of 64.  Reference citations are relative to /root/reference.
+ * All row-major.  T = B*L tokens, H = the hidden size (256 | 512 | 768 | 1024 for the row operators, MAG and the MAG-BERT engine;
+ * the MAG-XLNet engine: 768), heads of 64.  Reference citations are relative to /root/reference.
  */
 #ifndef MAGBERT_HIP_H
 #define MAGBERT_HIP_H
@@ -134,6 +135,8 @@ int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n
  * The whole MAG_BertForSequenceClassification forward / backward (bert.py:240-324 -> :76-237 -> modeling.py) as a
  * native step executor: one call enqueues every kernel of the pass on the stream (no Python between launches).   */
 typedef struct {
+    /* hidden_size: 256 | 512 | 768 (bert-base) | 1024 (bert-large) with num_heads * 64 == hidden_size; num_layers >= 1;
+     * intermediate_size % 128 == 0.  Anything else: mb_bert_create returns MB_ERR_SHAPE.                            */
     int vocab_size, hidden_size, num_layers, num_heads, intermediate_size, max_position, type_vocab, num_labels;
     int visual_dim, acoustic_dim, pad_token_id;
     float layer_norm_eps, mag_layer_norm_eps, beta_shift;

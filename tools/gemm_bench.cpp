@@ -2,7 +2,8 @@
 // Measurement tooling (not product).  Every case runs `reps` launches over `nset` rotating operand sets (so that operands
 // come from HBM / Infinity Cache like inside a training step, not from a warm L2) between two HIP events.
 //
-//   gemm_bench [--T tokens] [--reps n] [--nset n] [--only substring] [--trace 1]
+//   gemm_bench [--T tokens] [--reps n] [--nset n] [--only substring] [--trace 1] [--tile code] [--wtile 64|128|256] [--hidden H] [--inter I]
+//   --hidden / --inter: the layer's widths (default 768 / 3072, which is what the case names say; other sizes are printed behind the name)
 //   --trace 1 (with MB_GEMM_TRACE=1): after timing a case, one more launch whose per-block phase stamps are summarised
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -31,7 +32,7 @@ static void* dev_rand(size_t n_bf16, uint32_t seed) {
 }
 
 int main(int argc, char** argv) {
-    int T = 2400, reps = 48, nset = 6, trace = 0, looptrace = 0, tile = 0, wtile = 128;
+    int T = 2400, reps = 48, nset = 6, trace = 0, looptrace = 0, tile = 0, wtile = 128, H = 768, I = 0;
     std::string only;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i];
@@ -40,9 +41,12 @@ int main(int argc, char** argv) {
         else if (k == "--trace") trace = atoi(argv[i + 1]);
         else if (k == "--tile") tile = atoi(argv[i + 1]);          // mb_gemm tile code for every case (0 = auto, 64 | 128 | 256)
         else if (k == "--wtile") wtile = atoi(argv[i + 1]);        // grouped weight-gradient tile (64 | 128 | 256 = 256 x 128 ping-pong)
+        else if (k == "--hidden") H = atoi(argv[i + 1]); else if (k == "--inter") I = atoi(argv[i + 1]);
         else if (k == "--looptrace") { looptrace = atoi(argv[i + 1]); trace = trace || looptrace; }   // library built with -DMB_GEMM_LOOPTRACE
     }
-    const int H = 768, I = 3072;
+    if (I <= 0) I = 4 * H;
+    char sz[48] = "";
+    if (H != 768 || I != 3072) snprintf(sz, sizeof sz, "  (H=%d I=%d tile=%d)", H, I, tile);
     const int Tp = (T + 63) / 64 * 64;
     hipStream_t st; HCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     std::vector<void*> xh(nset), xi(nset), x3(nset), oi(nset), oi2(nset), o3(nset);
@@ -166,7 +170,7 @@ int main(int argc, char** argv) {
         HCK(hipEventRecord(e1, st)); HCK(hipEventSynchronize(e1));
         float ms; HCK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps, fl = 2.0 * c.M * c.N * c.K;
-        printf("%-52s %8.2f us %8.1f TF/s\n", c.name, us, fl / us * 1e-6);
+        printf("%-52s %8.2f us %8.1f TF/s%s\n", c.name, us, fl / us * 1e-6, sz);
         tot_us += us; tot_fl += fl;
         if (trace) { for (int i = 0; i < 8; ++i) launch(i); trace_summary(); }
     }
@@ -185,7 +189,7 @@ int main(int argc, char** argv) {
         float ms; HCK(hipEventElapsedTime(&ms, e0, e1));
         double fl = 0; for (int g = 0; g < 4; ++g) fl += 2.0 * gM[g] * gN[g] * Tp;
         const double us = ms * 1e3 / reps;
-        printf("%-52s %8.2f us %8.1f TF/s\n", "wgrad x4 grouped [768x3072|3072x768|768x768|2304x768]", us, fl / us * 1e-6);
+        printf("%-52s %8.2f us %8.1f TF/s%s wtile=%d\n", "wgrad x4 grouped [768x3072|3072x768|768x768|2304x768]", us, fl / us * 1e-6, sz, wtile);
         tot_us += us; tot_fl += fl;
         if (trace) { for (int i = 0; i < 8; ++i) launch(i); trace_summary(); }
     }

@@ -5,6 +5,8 @@
 // plain C++ process, so a GPU-box visit costs seconds instead of a Python/torch start-up, and rocprofv3 can wrap it.
 //
 //   step_bench [--model bert|xlnet] [--steps K] [--warmup W] [--batch B] [--seq L] [--dtype bf16|fp32] [--visual V] [--layers N]
+//              [--hidden H] [--heads n] [--inter I]       (MAG-BERT only; bert-large-uncased = --layers 24 --hidden 1024 --heads 16 --inter 4096;
+//                                                          --heads defaults to H / 64, --inter to 4 H)
 //              [--graph 0|1|2] [--h2d 0|1|2] [--nbatch n] [--dp 0|1] [--wire fp32|bf16] [--sparse 0|1] [--timing 0|1] [--shard 0|1]
 //   --dp 1:  the data-parallel step, mb_bert_train_step_dp, with a ONE-rank RCCL communicator created here through the C ABI
 //            (mb_comm_unique_id / mb_comm_create_rccl): the N > 1 code path -- graph chain, comm stream, events, ncclAllReduce /
@@ -36,7 +38,7 @@ struct Batch { int64_t *ids, *seg, *mask; float *vis, *aco, *lab; };
 
 int main(int argc, char** argv) {
     int steps = 30, warmup = 5, B = 48, L = 50, V = 47, A = 74, layers = 12, graph = 0, h2d = 0, nbatch = 4, dtype = MB_DT_BF16;
-    int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0;
+    int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -45,12 +47,17 @@ int main(int argc, char** argv) {
         else if (k == "--dtype") dtype = strcmp(v, "fp32") == 0 ? MB_DT_F32 : MB_DT_BF16;
         else if (k == "--dp") dp = atoi(v); else if (k == "--sparse") sparse = atoi(v); else if (k == "--timing") timing = atoi(v);
         else if (k == "--shard") shard = atoi(v);
+        else if (k == "--hidden") hidden = atoi(v); else if (k == "--heads") heads = atoi(v); else if (k == "--inter") inter = atoi(v);
         else if (k == "--model") xl = strcmp(v, "xlnet") == 0;       // MAG-XLNet (BASELINE.json configs[3]): the single-call step only (--graph 1|2)
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
-        else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 1; }
+        else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard)\n", k.c_str()); return 1; }
     }
+    if (heads <= 0) heads = hidden / 64;
+    if (inter <= 0) inter = 4 * hidden;
+    if (xl && hidden != 768) { fprintf(stderr, "--hidden/--heads/--inter: MAG-BERT only (the MAG-XLNet engine is built for 768)\n"); return 1; }
     mb_bert_config c = {};
-    c.vocab_size = 30522; c.hidden_size = 768; c.num_layers = layers; c.num_heads = 12; c.intermediate_size = 3072;
+    c.vocab_size = 30522; c.hidden_size = hidden; c.num_layers = layers; c.num_heads = heads; c.intermediate_size = inter;
     c.max_position = 512; c.type_vocab = 2; c.num_labels = 1; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
     c.layer_norm_eps = 1e-12f; c.mag_layer_norm_eps = 1e-5f; c.beta_shift = 1.0f;
     c.hidden_dropout = 0.1f; c.attn_dropout = 0.1f; c.mag_dropout = 0.5f; c.dtype = dtype; c.max_batch = B; c.max_seq = L;
@@ -177,9 +184,11 @@ int main(int argc, char** argv) {
     float hl[2]; HCK(hipMemcpy(hl, loss, 8, hipMemcpyDeviceToHost));
     const double host_ms = std::chrono::duration<double, std::milli>(t1 - t0).count() / steps;
     const double wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count() / steps;
-    printf("step_bench %sdtype=%s B=%d L=%d V=%d layers=%d graph=%d h2d=%d : %.3f ms/step (events) %.3f ms/step (wall) host-enqueue %.3f ms/step "
+    char shape[64] = "";
+    if (!xl && (hidden != 768 || heads != 12 || inter != 3072)) snprintf(shape, sizeof shape, " hidden=%d heads=%d inter=%d", hidden, heads, inter);
+    printf("step_bench %sdtype=%s B=%d L=%d V=%d layers=%d%s graph=%d h2d=%d : %.3f ms/step (events) %.3f ms/step (wall) host-enqueue %.3f ms/step "
            "%.1f samples/s last-loss %.4f mean-loss %.4f\n",
-           xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
+           xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, shape, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
            hl[1] / (steps + warmup));
     if (comm) {
         float ex = 0.f; size_t pieces = 0, cbytes = 0;
