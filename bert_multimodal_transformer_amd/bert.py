@@ -537,8 +537,6 @@ class _Core(object):
         """why one optimizer step cannot be ONE engine call (mb_bert_train_step), or None"""
         if self.stage_hooks:
             return "backward stage hooks are installed (data parallel: the gradient exchange is issued between stages)"
-        if self.kind == "xlnet" and os.environ.get("MB_OVERLAP_WGRAD", "0") not in ("", "0"):
-            return "MB_OVERLAP_WGRAD=1: the side-stream weight gradients of MAG-XLNet are driven stage by stage"
         return None
 
     def train_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, opt, loss_scale=1.0, mode=2, comm=None):
@@ -996,7 +994,7 @@ class _FusedStep(object):
         # data parallel, MB_DP_GRAPH=1: one replayed graph per pass / backward stage instead of kernel launches from Python.  Opt-in:
         # measured on one GPU (1-rank RCCL group, profiles/r03_dp_force.txt) the graphs are not faster (4.52 vs 4.43 ms per step; the
         # single-call step: 3.84) -- what the stage-driven step pays is the exchange machinery itself, not the launches
-        if core.kind == "bert" and core.stage_hooks and os.environ.get("MB_DP_GRAPH", "0") == "1" and os.environ.get("MB_OVERLAP_WGRAD", "0") in ("", "0"):
+        if core.kind == "bert" and core.stage_hooks and os.environ.get("MB_DP_GRAPH", "0") == "1":
             core.stage_step(input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, loss_scale=loss_scale)
             return core.loss_buf[0]
         core.forward(input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, True)
@@ -1024,7 +1022,7 @@ class _FusedStep(object):
         dp = getattr(optimizer, "_dp", None) if optimizer is not None else None
         mdp = getattr(self, "_dp", None)
         if optimizer is None and mdp is not None and not mdp.sync and mdp.micro_ready() and graph is not False and \
-                core.kind in ("bert", "xlnet") and os.environ.get("MB_OVERLAP_WGRAD", "0") in ("", "0"):
+                core.kind in ("bert", "xlnet"):
             # gradient-accumulation micro-step of a data-parallel rank (multimodal_driver.py:375-376, 383): nothing is exchanged, so it is the
             # plain single call without the optimizer (the backward accumulates); the exchange of the step that ends the window
             # moves the word-embedding table densely (distributed.DataParallel._micro_since_sync)
@@ -1034,8 +1032,7 @@ class _FusedStep(object):
             mdp._micro_since_sync += 1
             mdp._last_fused = True
             return core.loss_buf[0]
-        if dp is not None and graph is not False and dp.fused_ready() and core.kind in ("bert", "xlnet") and \
-                os.environ.get("MB_OVERLAP_WGRAD", "0") in ("", "0"):
+        if dp is not None and graph is not False and dp.fused_ready() and core.kind in ("bert", "xlnet"):
             # data parallel: the same single call with the gradient exchange inside (mb_*_train_step_dp, distributed.Comm)
             opt = optimizer.flat_step_args(core, allow_dp=True)
             comm = None

@@ -32,7 +32,8 @@ struct mb_bert_engine : StepMixin {
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
     std::vector<size_t> ws_x;
     std::vector<LayerWs> lw;
-    size_t ws_ds[2], ws_dzd[2], ws_ds2[2], ws_dzd2[2], ws_du[2], ws_dqkv[2];   // dY operands of the wgrads: ping-pong by layer parity
+    size_t ws_ds[2], ws_dzd[2], ws_ds2[2], ws_dzd2[2], ws_du[2], ws_dqkv[2];   // dY operands of the wgrads: ping-pong by layer parity (the workspace layout of the
+                                                                               // retired side-stream scheme: every reader of a layer's set now runs inside that layer's stage)
     size_t ws_dxa, ws_dxb, ws_dctx, ws_dsum, ws_dz, ws_lnp_a, ws_lnp_b;
     size_t lnp_stride = 0;         // floats per layer in each of the two LayerNorm partial buffers
     int lnp_nblk = 0;              // slabs per layer written by the current backward
@@ -44,11 +45,6 @@ struct mb_bert_engine : StepMixin {
     const int64_t* ids = nullptr; const int64_t* seg = nullptr; const int64_t* mask = nullptr;
     int B = 0, L = 0, training = 0;
     int padT = -1;                 // token count whose pad rows [T, Tp) are currently known to be zero
-    // weight-gradient GEMMs run on an internal side stream, concurrently with the dgrad chain of the same layer
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> evs;      // 5 events per encoder stage (4 forks + 1 join), never reused within a backward
-    int overlap_wgrad = 0;         // MB_OVERLAP_WGRAD=1: weight-gradient launches on the internal side stream (round-1 default; measured equal
-                                   // to the in-line grouped launch, which keeps the step a single-stream sequence -- and its hipGraph a fast one)
     // MB_ADAMW_OVERLAP=C: the single-call step forks the optimizer of every finished chunk of C layers onto this stream (enqueue_step)
     int opt_chunk = 0;
     int prefetch = 1;              // MB_PREFETCH=0: the LayerNorm kernels do not touch the next GEMMs' weights (common.h Prefetch).  Touching
@@ -64,22 +60,17 @@ struct mb_bert_engine : StepMixin {
     // MB_ADAMW_RIDE=1 (kernels.h AdamRide): in a single-process single-call step the grouped weight-gradient launch of layer l carries
     // the optimizer update of layer l+1's GEMM weights (whose gradients the launch before completed) as extra workgroups in the slots
     // its tiles leave empty (256 x 128 tiles: 40 of 256 CUs; 128 x 128: 80 of 512 slots); the sweep at the end skips those layers.
-    int adam_ride = 1, ride_blocks = 0;
+    RideOpts ride_opts;            // (engine_common.h: the rider switches both engines have)
+    int ride_blocks = 0;           // MB_ADAMW_RIDE_BLOCKS: rider workgroups per weight-gradient launch (0 = every free slot)
     float* ride_m = nullptr; float* ride_v = nullptr;       // Adam moments of the step being enqueued, when riders apply to it
     size_t ride_cursor = 0;                                 // the riders of the step being enqueued have taken [ride_cursor, wp) of the decay slab
     bool one_sweep = true;                                  // MB_ADAMW_ONE_SWEEP=0: the end-of-step sweep as three launches (kernels.h AdamRanges)
     long ride_params = 0;                                   // MB_ADAMW_RIDE_PARAMS: parameters per launch (0 = by the token count)
-    // MB_ADAMW_RIDE_DGRAD >= 1: riders also in the two 64 x 64 dgrad launches of a layer (ffn1, qkv: 456 tiles in 768 block slots at T = 2400;
-    // kernels.h gemm_nn_ride_launch), 2 (default): and in the 128 x 128 ffn2 dgrad (456 tiles in 512 slots: 56 CUs hold one tile).
-    // _PARAMS: parameters per 64 x 64 launch (0 = by the launch's FLOPs), _DGELU_PARAMS: per ffn2 launch (0 = 14,336 per free slot),
-    // _BLOCKS: rider workgroups (0 = every free slot).  Same box: 3.422 ms off | 3.411 (1) | 3.401 (2)  (profiles/r06_adamw_ride_dgrad.txt)
-    int ride_dgrad = 2, ride_dgrad_blocks = 0;
-    int ride_attn = 1, ride_attn_blocks = 0;                // MB_ADAMW_RIDE_ATTN: riders in the attention backward launch (_BLOCKS, _PARAMS: as above)
-    long ride_attn_params = 0;
-    long ride_dgrad_params = 0, ride_dgelu_params = 0;      // (MB_ADAMW_RIDE_DGRAD=2: also the ffn2 dgrad; _DGELU_PARAMS: parameters per such launch)
+    // (ride_opts.dgrad: riders also in the two narrow dgrad launches of a layer -- ffn1, qkv: 456 64 x 64 tiles in 768 block slots at T = 2400;
+    //  kernels.h gemm_nn_ride_launch -- and, at 2, in the 128 x 128 ffn2 dgrad: 456 tiles in 512 slots, 56 CUs hold one tile.
+    //  Same box: 3.422 ms off | 3.411 (1) | 3.401 (2)  (profiles/r06_adamw_ride_dgrad.txt))
     int group_wgrad = 256;         // MB_GROUP_WGRAD: tile of the per-layer grouped wgrad launch (64 | 128 | 256 = 256 x 128 ping-pong), 0 = four launches
-    bool grouped = false;          // the layer's four weight gradients are ONE launch
-    bool deferred = false;         // ... on the side stream, joined one stage later (MB_OVERLAP_WGRAD=0: on the caller's stream, in line)
+    bool grouped = false;          // the layer's four weight gradients are ONE launch, in line on the caller's stream
     float* attn_out = nullptr;     // mb_bert_set_attention_output: [num_layers][B][nh][L][L] fp32, filled by the next forwards
     const float* head_mask = nullptr;   // mb_bert_set_head_mask: [num_layers][num_heads] fp32 (caller-owned device memory)
     const float* emb_in = nullptr;      // mb_bert_set_inputs_embeds: [B*L][H] fp32 word embeddings given instead of input_ids
@@ -167,13 +158,7 @@ static void build_layout(mb_bert_engine* e) {
     Carver w;
     e->mw.init(c.dtype, (int)T, (int)H, (int)V, (int)A);
     e->ws_mag = w.take(e->mw.bytes);
-    {   // MB_PROLOGUE_PACK=0: the step prologue stages the fp32 modality tensors and the forward packs them (two more launches)
-        const char* pv = getenv("MB_PROLOGUE_PACK");
-        e->pk_enable = !(pv && atoi(pv) == 0);
-        e->pk_vis = e->ws_mag + e->mw.vp; e->pk_aco = e->ws_mag + e->mw.ap; e->pk_Vp = e->mw.Vp; e->pk_Ap = e->mw.Ap; e->pk_dtype = c.dtype;
-        const char* pw = getenv("MB_PROLOGUE_PACKW");
-        e->pkw_enable = !(pw && atoi(pw) == 0);
-    }
+    e->pk_vis = e->ws_mag + e->mw.vp; e->pk_aco = e->ws_mag + e->mw.ap; e->pk_Vp = e->mw.Vp; e->pk_Ap = e->mw.Ap; e->pk_dtype = c.dtype;
     e->ws_emb = w.take(T * H * es);
     e->ws_emb_st = w.take(2 * T * 4);
     e->ws_x.resize(c.num_layers + 1);
@@ -206,12 +191,12 @@ static void build_layout(mb_bert_engine* e) {
     e->ws_lnp_a = w.take(e->lnp_stride * 4 * (c.num_layers + 2)); e->ws_lnp_b = w.take(e->lnp_stride * 4 * (c.num_layers + 2));     // (+1: MAG's gate, +1: the embeddings)
     e->carve_step(w, T, (int)V, (int)A, c.max_batch, c.num_labels, SITE_LAYER0 + 4 * c.num_layers);
     e->idcnt_off = w.take((size_t)c.vocab_size * 4);          // token-id occurrence table of the single-call step (MB_EMBED_UNIQUE=0: off)
-    { const char* uv = getenv("MB_EMBED_UNIQUE"); e->idcnt_enable = !(uv && atoi(uv) == 0); }
+    e->idcnt_enable = env_on("MB_EMBED_UNIQUE", true);
     // stamps of the word rows a step touched + the sweep's two state words (StepMixin::stamp_live; MB_ADAMW_SKIP_ZERO_ROWS=0: full read)
     e->stamp_rows = (size_t)c.vocab_size;
     e->stamp_off = w.take(((size_t)c.vocab_size + 2) * 4);
-    { const char* sv = getenv("MB_ADAMW_SKIP_ZERO_ROWS"); e->stamp_enable = !(sv && atoi(sv) == 0); }
-    { const char* ov = getenv("MB_ADAMW_ONE_SWEEP"); e->one_sweep = !(ov && atoi(ov) == 0); }
+    e->stamp_enable = env_on("MB_ADAMW_SKIP_ZERO_ROWS", true);
+    e->one_sweep = env_on("MB_ADAMW_ONE_SWEEP", true);
     if (e->deterministic) {          // shadow accumulator of everything behind the layers' GEMM weights (those have ONE writer per element)
         e->det_begin = e->wp; e->det_end = e->n_params;
         e->ws_det = w.take((e->det_end - e->det_begin) * sizeof(long long));
@@ -219,31 +204,13 @@ static void build_layout(mb_bert_engine* e) {
     e->ws_bytes = w.off;
 }
 
-// the internal side stream + its fork / join events (created once, outside any stream capture)
-static int ensure_side(mb_bert_engine* e) {
-    if (e->side || !e->overlap_wgrad) return MB_OK;
-    // MB_SIDE_PRIORITY=1: lowest dispatch priority for the weight-gradient stream (the dgrad chain is the critical
-    // path).  Measured: no effect -- resident wgrad blocks keep their LDS slots for a whole K = T loop, priority
-    // only orders NEW workgroups -- so the default stays the normal priority.
-    int least = 0, greatest = 0;
-    CK((int)hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const char* pv = getenv("MB_SIDE_PRIORITY");
-    const int prio = (pv && atoi(pv) != 0) ? least : 0;
-    CK((int)hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, prio));
-    e->evs.assign((size_t)e->c.num_layers * 5, nullptr);
-    for (auto& ev : e->evs) CK((int)hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    return MB_OK;
-}
-
-// State the next pass relies on but that is not part of the pass itself (kept out of captured step graphs): outstanding
-// side-stream work of an unfinished backward, the one-time clearing of the workspace, zero pad rows for this token count.
+// State the next pass relies on but that is not part of the pass itself (kept out of captured step graphs): the one-time
+// clearing of the workspace, zero pad rows for this token count.
 static int prepare_pass(mb_bert_engine* e, int T, hipStream_t st) {
     const mb_bert_config& c = e->c;
     const int H = c.hidden_size, I = c.intermediate_size, dt = c.dtype;
     char* ws = e->ws;
     const int Tp = (int)align_up((size_t)T, 64);
-    if (e->deferred && e->side)       // a backward that was not run to its last stage may still have weight-gradient GEMMs reading activations
-        for (size_t l = 0; l < 2 && l * 5 + 4 < e->evs.size(); ++l) CK((int)hipStreamWaitEvent(st, e->evs[l * 5 + 4], 0));
     if (!e->ws_zeroed) { CK((int)hipMemsetAsync(ws, 0, e->ws_bytes, st)); e->ws_zeroed = true; e->padT = T; }
     if (e->padT != T && Tp > T) {
         // a different batch shape ran before: rows [T, Tp) of every buffer that feeds a wgrad as the k-major operand
@@ -426,31 +393,20 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
     mb_bert_engine* e = new mb_bert_engine();
     e->c = *cfg;
-    if (const char* v = getenv("MB_OVERLAP_WGRAD")) e->overlap_wgrad = atoi(v);
-    if (const char* v = getenv("MB_GROUP_WGRAD")) e->group_wgrad = atoi(v);
-    if (const char* v = getenv("MB_WGRAD_OVERWRITE")) e->ow_enable = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_KEEP")) e->keep_enable = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_IN_WGRAD")) e->adam_in_wgrad = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE")) e->adam_ride = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_BLOCKS")) e->ride_blocks = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_PARAMS")) e->ride_params = atol(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD")) e->ride_dgrad = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD_BLOCKS")) e->ride_dgrad_blocks = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD_PARAMS")) e->ride_dgrad_params = atol(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGELU_PARAMS")) e->ride_dgelu_params = atol(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN")) e->ride_attn = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN_BLOCKS")) e->ride_attn_blocks = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN_PARAMS")) e->ride_attn_params = atol(v);
-    if (const char* v = getenv("MB_DETERMINISTIC")) e->deterministic = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_OVERLAP")) e->opt_chunk = atoi(v);
-    if (const char* v = getenv("MB_PREFETCH")) e->prefetch = atoi(v);
-    if (const char* v = getenv("MB_PF_QKV")) e->pf_qkv = atoi(v);
+    e->read_env();
+    e->ride_opts.read_env();
+    e->group_wgrad = env_int("MB_GROUP_WGRAD", e->group_wgrad);
+    e->adam_in_wgrad = env_int("MB_ADAMW_IN_WGRAD", e->adam_in_wgrad);
+    e->ride_blocks = env_int("MB_ADAMW_RIDE_BLOCKS", e->ride_blocks);
+    e->ride_params = env_long("MB_ADAMW_RIDE_PARAMS", e->ride_params);
+    e->opt_chunk = env_int("MB_ADAMW_OVERLAP", e->opt_chunk);
+    e->prefetch = env_int("MB_PREFETCH", e->prefetch);
+    e->pf_qkv = env_int("MB_PF_QKV", e->pf_qkv);
     if (e->adam_in_wgrad && !getenv("MB_GROUP_WGRAD")) e->group_wgrad = 128;      // (that experiment lives in the 128 x 128 kernel's epilogue)
     // 256 = the 256 x 128 ping-pong tile (gemm_pp.hip; bf16 only): falls back to 128 where it does not divide the layer
     if (e->group_wgrad == 256 && (cfg->dtype != DT_BF16 || cfg->hidden_size % 256 != 0 || cfg->intermediate_size % 256 != 0)) e->group_wgrad = 128;
     e->grouped = (e->group_wgrad == 64 || e->group_wgrad == 128 || e->group_wgrad == 256) && cfg->hidden_size % e->group_wgrad == 0 &&
                  cfg->intermediate_size % e->group_wgrad == 0;
-    e->deferred = e->overlap_wgrad && e->grouped;
 
     build_layout(e);
     // lazy zeroing: the range the grouped launches of all layers store into = every layer's four GEMM weights (contiguous)
@@ -461,8 +417,6 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
 }
 void mb_bert_destroy(mb_bert_engine* e) {
     if (!e) return;
-    if (e->side) hipStreamDestroy(e->side);
-    for (auto& ev : e->evs) if (ev) hipEventDestroy(ev);
     if (e->opt_side) hipStreamDestroy(e->opt_side);
     for (auto& ev : e->opt_ev) if (ev) hipEventDestroy(ev);
     e->destroy_prof();
@@ -646,27 +600,13 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             const LayerWs& w = e->lw[l];
             char* dx = ws + e->ws_dxa;     // grad wrt x[l+1] on entry, wrt x[l] on exit
             char* dy1 = ws + e->ws_dxb;
-            const int par = l & 1;                      // the grouped wgrad of layer l reads these while layer l-1 runs
+            const int par = l & 1;
             char* dsA = ws + e->ws_ds[par];             // LN2 (FFN output) backward
             char* dzdA = hd ? ws + e->ws_dzd[par] : dsA;
             char* dsB = ws + e->ws_ds2[par];            // LN1 (attention output) backward
             char* dzdB = hd ? ws + e->ws_dzd2[par] : dsB;
             char* du = ws + e->ws_du[par];
             char* dqkv = ws + e->ws_dqkv[par];
-            // wgrad GEMMs go to the side stream: they only read (dY, saved X) and accumulate into G, so they overlap the
-            // dgrad chain; dY buffers are per-LayerNorm (A/B) and the stage ends with a join, which keeps them race-free.
-            hipStream_t ss = st;
-            if (e->overlap_wgrad) {
-                CK(ensure_side(e));
-                ss = e->side;
-            }
-            hipEvent_t* sev = e->overlap_wgrad ? &e->evs[(size_t)l * 5] : nullptr;
-            auto fork = [&](int k) -> int {      // side stream may start once main has produced dY number k
-                if (ss == st) return 0;
-                int r = (int)hipEventRecord(sev[k], st);
-                if (r) return r;
-                return (int)hipStreamWaitEvent(ss, sev[k], 0);
-            };
             int nblk = 0;
             float* lnp_a = (float*)(ws + e->ws_lnp_a) + (size_t)l * e->lnp_stride;
             float* lnp_b = (float*)(ws + e->ws_lnp_b) + (size_t)l * e->lnp_stride;
@@ -678,7 +618,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                     // ... and touches W1 | W2 for the two FFN dgrads behind it (common.h Prefetch)
                                     Prefetch{e->prefetch ? e->W(o.w1) : nullptr, (size_t)2 * I * H * (dt == DT_BF16 ? 2 : 4), nullptr}));
             // The four weight gradients of the layer: one grouped launch once dqkv exists (MB_GROUP_WGRAD=0: four launches,
-            // each forked as soon as its dY is final).
+            // each as soon as its dY is final).
             GemmArgs wg[4] = {wgrad_args(H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I),
                               wgrad_args(I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H),
                               wgrad_args(H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H),
@@ -686,7 +626,6 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             const bool grouped = e->grouped;
             if (grouped)
                 for (GemmArgs& a : wg) a.overwrite = e->ow_pass ? 1 : 0;       // whole-tile, no split-K launches only
-            const bool inl = grouped && !e->deferred;         // grouped launch in line on the caller's stream (no overlap)
             // dX = dY . W + R (GEMM_NN, EPI_ADD_RES), with riders when the launch is the 64 x 64 three-slot kernel and leaves block slots free
             // (Touching the forward activations the grouped weight gradient multiplies with -- g, y1, x_l, 22 MB from HBM -- makes that launch
             //  1.2 .. 3.2 us faster, but every carrier tried pays more than that: separate launches 3 x 4.7 us, the attention backward +1.8 ..
@@ -694,23 +633,16 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             // (mode EPI_DGELU: the ffn2 dgrad with the fused bias gradient `colsum`; 56 of its CUs hold one tile instead of two)
             auto dgrad_ride = [&](int mode, int Mo, int No, int Ko, const void* dY, int ldy, const void* Wt, int ldw, void* dX, int ldx, const void* R, int ldr,
                                   float* colsum) -> int {
-                const RideOpts ro = {e->ride_dgrad, e->ride_dgrad_blocks, e->ride_dgrad_params, e->ride_dgelu_params};
-                return dgrad_with_riders(dt, mode, Mo, No, Ko, dY, ldy, Wt, ldw, dX, ldx, R, ldr, colsum, kNoDrop, acc, st, inl && e->ride_m != nullptr, ro,
-                                         e->cu_count(), [&](size_t budget, int blocks) { return take_ride(l, budget, blocks); });
+                return dgrad_with_riders(dt, mode, Mo, No, Ko, dY, ldy, Wt, ldw, dX, ldx, R, ldr, colsum, kNoDrop, acc, st, grouped && e->ride_m != nullptr,
+                                         e->ride_opts, e->cu_count(), [&](size_t budget, int blocks) { return take_ride(l, budget, blocks); });
             };
             int wtile = e->group_wgrad;
             if (grouped && wtile == 256 && !gemm_grouped_tn_ok(dt, wg, 4, 256)) wtile = 128;      // (fewer than three k stages: the 128 x 128 kernel)
             if (grouped && !gemm_grouped_tn_ok(dt, wg, 4, wtile)) return MB_ERR_SHAPE;
-            if (!grouped) {
-            CK(fork(0));
-            CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, ss));
-            }
+            if (!grouped) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
             // du = (dzd . W2) * gelu'(u), with the intermediate bias gradient (column sums of du) fused into the epilogue
             CK(dgrad_ride(EPI_DGELU, T, I, H, dzdA, H, e->W(o.w2), I, du, I, ws + w.u, I, G + o.b1));
-            if (!grouped) {
-            CK(fork(1));
-            CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, ss));
-            }
+            if (!grouped) CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, st));
             CK(dgrad_ride(EPI_ADD_RES, T, H, I, du, I, e->W(o.w1), H, dy1, H, dsA, H, nullptr));
             // LN1 + dropout backward
             Prefetch pf_attn = {e->prefetch ? e->W(o.wqkv) : nullptr, (size_t)4 * H * H * (dt == DT_BF16 ? 2 : 4), nullptr};
@@ -725,10 +657,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                     // ... Wqkv | Wo for the attention-side dgrads, and with the loads that leaves over the q | k | v (+ context)
                                     // rows this layer saved in the forward, which the attention backward two launches on finds in HBM
                                     pf_attn));
-            if (!grouped) {
-            CK(fork(2));
-            CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H, ss));
-            }
+            if (!grouped) CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H, st));
             e->lnp_nblk = nblk;
             if (!defer_ln) {
                 float* const dst6[6] = {G + o.ln2w, G + o.ln2b, G + o.b2, G + o.ln1w, G + o.ln1b, G + o.bo};
@@ -740,9 +669,9 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             // (riders: the launch's empty block slots -- L <= 64: 448 of 1024 next to a latency-bound kernel; L = 128: the 128 CUs its second
             //  round leaves idle -- carry a piece of the optimizer update; MB_ADAMW_RIDE_ATTN=0 turns them off)
             AdamRide ra = {};
-            if (e->ride_attn && inl && e->ride_m && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
+            if (e->ride_opts.attn && grouped && e->ride_m && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
                 int free_slots = attention_backward_free_slots(dt, L, B * nh, e->cu_count());
-                if (e->ride_attn_blocks > 0 && free_slots > 0) free_slots = e->ride_attn_blocks;      // (fp32 has no rider kernel: 0 stays 0, or the slice a rider took would be skipped)
+                if (e->ride_opts.attn_blocks > 0 && free_slots > 0) free_slots = e->ride_opts.attn_blocks;      // (fp32 has no rider kernel: 0 stays 0, or the slice a rider took would be skipped)
                 const int blocks = std::min(free_slots, 2 * e->cu_count()) / 8 * 8;
                 if (blocks >= 8) {
                     // L = 128: 128 whole CUs for about half the launch (~41 GB/s each): 20,480 parameters per rider workgroup -- same box, B = 32:
@@ -752,7 +681,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                     // the 128 x 64 ping-pong tile, whose 16 idle CUs carry 0.2 - 0.26 M where the 64 x 64 kernel's free slots carried 1.25 M:
                     // with the sweep that much longer the optimum moved up -- 3.169 ms at 2.5 M | 3.157 at 3 M | 3.152 at 3.5 M | 3.140 at 4 M
                     // (this: 1,650 per token) | 3.140 at 4.5 M (profiles/r06_ride_budget3.txt)
-                    const size_t budget = e->ride_attn_params > 0 ? (size_t)e->ride_attn_params
+                    const size_t budget = e->ride_opts.attn_params > 0 ? (size_t)e->ride_opts.attn_params
                                                                   : (L > 64 ? (size_t)blocks * 20480 : (size_t)1650 * (size_t)T);
                     ra = take_ride(l, budget / 1024 * 1024, blocks);
                 }
@@ -763,7 +692,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                   e->attn_stats(w)));
             // (experiment) the update inside the launch: the tile of the gradient becomes the new parameters -- so every reader of the
             // OLD weights of this layer (the qkv dgrad below) goes first
-            const bool fuse = inl && e->fuse_m && e->fuse_v && e->ow_pass && e->group_wgrad == 128;
+            const bool fuse = grouped && e->fuse_m && e->fuse_v && e->ow_pass && e->group_wgrad == 128;
             if (fuse) {
                 const size_t offs[4] = {o.w2, o.w1, o.wo, o.wqkv};
                 for (int k = 0; k < 4; ++k) {
@@ -776,7 +705,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             }
             // riders: an optimizer update in the empty slots of this launch (take_ride, below the loop header)
             AdamRide ride = {};
-            if (inl && !fuse) {
+            if (grouped && !fuse) {
                 int tiles = 0;
                 const int bm = wtile == 256 ? 256 : wtile, bn = wtile == 256 ? 128 : wtile;
                 for (const GemmArgs& a : wg) tiles += (a.M / bm) * (a.N / bn);
@@ -786,36 +715,16 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                 const size_t budget = e->ride_params > 0 ? (size_t)e->ride_params : std::min((size_t)1000 * (size_t)Tk, (size_t)1100000 + (size_t)590 * (size_t)Tk);
                 ride = take_ride(l, budget, e->ride_blocks > 0 ? e->ride_blocks : (slots - tiles) / 8 * 8);
             }
-            auto launch_group = [&]() -> int {
-                if (inl) {
-                    if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], st));
-                    CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, fuse, ride.blocks ? &ride : nullptr));
-                    if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], st));
-                    return MB_OK;
-                }
-                CK(fork(3));
-                if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], ss));
-                CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, ss));
-                if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], ss));
-                return (int)hipEventRecord(sev[4], ss);       // "weight gradients (or updated weights) of layer l are final"
-            };
-            if (grouped) CK(launch_group());
-            if (!grouped) {
-                CK(fork(3));
-                CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, ss));
+            if (grouped) {
+                if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], st));
+                CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, fuse, ride.blocks ? &ride : nullptr));
+                if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], st));
+            } else {
+                CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, st));
             }
             if (!fuse) CK(dgrad_ride(EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, dsB, H, nullptr));
-            if (ss != st && !grouped) {      // join: the stage's gradients are complete (and dY buffers reusable) once main passes this
-                CK((int)hipEventRecord(sev[4], ss));
-                CK((int)hipStreamWaitEvent(st, sev[4], 0));
-            }
-            // deferred join: the grouped wgrad of layer l keeps running under the dgrad chain of layer l-1; main only
-            // waits for layer l+1's (whose dY buffers, same parity as l-1, are written next).  What is final on `st` when
-            // this stage returns is therefore: weights of layer l+1, biases / LayerNorm of layer l (mb_bert_stage_grad_ranges)
-            if (e->deferred && l + 1 < NL) CK((int)hipStreamWaitEvent(st, e->evs[(size_t)(l + 1) * 5 + 4], 0));
         } else {
             // ---- MAG + embeddings
-            if (e->deferred && e->side) CK((int)hipStreamWaitEvent(st, e->evs[4], 0));      // weight gradients of layer 0
             char* dx = ws + e->ws_dxa;
             char* de = ws + e->ws_dxb;
             // single-call step: the six column sums of MAG's gate go to partial slabs like the LayerNorm ones, and ONE launch reduces
@@ -870,7 +779,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
 // One optimizer step of train_epoch (/root/reference/multimodal_driver.py:354-388: batch -> forward -> MSE -> backward ->
 // optimizer.step() -> optimizer.zero_grad()) as two launches: the step prologue (this step's batch, dropout keys and AdamW
 // scalars into device memory) and a replayed hipGraph holding every other kernel of the step -- ONE in-order kernel sequence
-// (the grouped weight-gradient launches run in line: a graph with a side-stream fork / join replays on a slow path).
+// (a graph with a fork / join inside replays on a slow path).
 // mode 1 = graph replay (captured on first use per shape), mode 2 = the same kernel sequence launched one by one (A/B
 // reference for the graph; also what runs while profiling events are on).  The prologue also converts the modality tensors into
 // MAG's packed GEMM operands, counts the occurrences of every token id and clears the loss accumulator (rowops.hip).
@@ -911,12 +820,12 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
     const int se = nseg == 1 ? NL + 2 : (seg + 1 < nseg ? 1 + (seg + 1) * C : NL + 2);
     // (experiment) the layers' weights are updated by their own weight-gradient launches: single segment, known-zero gradients,
     // in-line 128 x 128 grouped launches, the layers' GEMM weights at the head of the decay slab
-    const bool fuse = e->adam_in_wgrad && m && v && nseg == 1 && e->ow_pass && e->grouped && !e->deferred && e->group_wgrad == 128 && NL > 0 &&
+    const bool fuse = e->adam_in_wgrad && m && v && nseg == 1 && e->ow_pass && e->grouped && e->group_wgrad == 128 && NL > 0 &&
                       e->lo[0].wqkv == 0 && !e->prof;
     e->fuse_m = fuse ? m : nullptr; e->fuse_v = fuse ? v : nullptr;
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside the weight-gradient launches of layers 0 .. NL-2; whether a launch
     // really carried one is decided there, so the sweep below asks the engine which layers are still to do
-    const bool ride = e->adam_ride && !fuse && m && v && nseg == 1 && e->grouped && !e->deferred && NL > 1 && e->lo[0].wqkv == 0 && !e->prof &&
+    const bool ride = e->ride_opts.ride && !fuse && m && v && nseg == 1 && e->grouped && NL > 1 && e->lo[0].wqkv == 0 && !e->prof &&
                       (e->group_wgrad == 128 || e->group_wgrad == 256);
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wp;
@@ -993,11 +902,10 @@ int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float*
     if ((m == nullptr) != (v == nullptr) || (mode != 1 && mode != 2)) return MB_ERR_ARG;
     const int T = B * L;
     char* ws = e->ws;
-    CK(ensure_side(e));
     e->training = 1;
     CK(prepare_pass(e, T, st));
     int nseg = 1;
-    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->overlap_wgrad && !e->prof) {
+    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof) {
         nseg = c.num_layers / e->opt_chunk + 1;
         if (!e->opt_side) {
             CK((int)hipStreamCreateWithFlags(&e->opt_side, hipStreamNonBlocking));
@@ -1102,7 +1010,7 @@ int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const flo
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if (!m || !v || (mode != 1 && mode != 2)) return MB_ERR_ARG;
-    if (e->overlap_wgrad || !e->grouped) return MB_ERR_MODE;      // the exchange's pieces assume a layer's weight gradients are final when its stage returns
+    if (!e->grouped) return MB_ERR_MODE;      // the exchange's pieces assume a layer's weight gradients are final when its stage returns
     const int NL = c.num_layers;
     const std::vector<int> plan = dp_chunk_plan(NL);
     const int nb = (int)plan.size();
@@ -1160,7 +1068,7 @@ int mb_bert_stage_forward(mb_bert_engine* e, const int64_t* input_ids, const flo
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if (mode != 1 && mode != 2) return MB_ERR_ARG;
-    if (e->head_mask || e->emb_in || e->pos_ids || e->deferred) return MB_ERR_MODE;
+    if (e->head_mask || e->emb_in || e->pos_ids) return MB_ERR_MODE;
     if (e->prof) mode = 2;              // timing events around kernels: launch by launch (events cannot live inside a captured graph)
     char* ws = e->ws;
     e->training = 1;
@@ -1182,7 +1090,6 @@ int mb_bert_stage_backward(mb_bert_engine* e, float loss_scale, int stage, int m
     hipStream_t st = (hipStream_t)stream;
     if (!e || !e->G || !e->ran_forward || !e->training) return MB_ERR_ARG;
     if (stage < 0 || stage > e->c.num_layers + 1 || (mode != 1 && mode != 2)) return MB_ERR_ARG;
-    if (e->deferred) return MB_ERR_MODE;
     if (e->prof) mode = 2;
     if (stage == 0) CK(e->begin_backward_pass(e->G, st));        // outside the graph: decides store vs accumulate (part of the graph's identity)
     const float* lab = (const float*)(e->ws + e->ws_in_lab);
@@ -1316,12 +1223,9 @@ int mb_bert_stage_grad_ranges(const mb_bert_engine* e, int stage, size_t* offs, 
     } else if (stage <= NL) {
         const int l = NL - stage;
         const LayerOff& o = e->lo[l];
-        auto wspan = [&](int k) { span(e->lo[k].wqkv, k + 1 < NL ? e->lo[k + 1].wqkv : e->wp); };
-        if (!e->deferred) wspan(l);
-        else if (l + 1 < NL) wspan(l + 1);       // deferred join: the weights arrive one stage late
+        span(o.wqkv, l + 1 < NL ? e->lo[l + 1].wqkv : e->wp);        // the layer's GEMM weights
         span(o.bqkv, l + 1 < NL ? e->lo[l + 1].bqkv : e->emb_lnw);
     } else if (stage == NL + 1) {
-        if (e->deferred) span(e->lo[0].wqkv, NL > 1 ? e->lo[1].wqkv : e->wp);
         span(e->word, e->wc);                                 // embeddings + MAG weights
         span(e->emb_lnw, e->bp);                              // embeddings LayerNorm
         span(e->mag_bhv, e->bc);                              // MAG biases + LayerNorm

@@ -24,6 +24,11 @@ struct TensorInfo {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// an environment switch, or `dflt` when it is not set (env_on: "0" turns it off, any other number on)
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+inline long env_long(const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; }
+inline bool env_on(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
+
 inline uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -127,7 +132,24 @@ inline long ride_pn_params() {       // MB_ADAMW_RIDE_PN_PARAMS: parameters per 
     if (v < 0) { const char* e = getenv("MB_ADAMW_RIDE_PN_PARAMS"); v = e ? atol(e) : 0; }
     return v;
 }
-struct RideOpts { int dgrad = 2, dgrad_blocks = 0; long dgrad_params = 0, dgelu_params = 0; };
+// The rider switches both engines have (kernels.h AdamRide).  MB_ADAMW_RIDE=0: no riders at all.  MB_ADAMW_RIDE_DGRAD >= 1: riders in the
+// narrow dgrad launches of a layer, 2 (default): and in the ffn2 dgrad (EPI_DGELU); _DGRAD_PARAMS / _DGELU_PARAMS: parameters per such launch
+// (0 = by the launch's size, below), _DGRAD_BLOCKS: rider workgroups (0 = every free slot).  MB_ADAMW_RIDE_ATTN: riders in the attention
+// backward launches (_ATTN_BLOCKS, _ATTN_PARAMS: as above; the budgets are the engines').
+struct RideOpts {
+    int dgrad = 2, dgrad_blocks = 0; long dgrad_params = 0, dgelu_params = 0;
+    int ride = 1, attn = 1, attn_blocks = 0; long attn_params = 0;
+    void read_env() {
+        ride = env_int("MB_ADAMW_RIDE", ride);
+        dgrad = env_int("MB_ADAMW_RIDE_DGRAD", dgrad);
+        dgrad_blocks = env_int("MB_ADAMW_RIDE_DGRAD_BLOCKS", dgrad_blocks);
+        dgrad_params = env_long("MB_ADAMW_RIDE_DGRAD_PARAMS", dgrad_params);
+        dgelu_params = env_long("MB_ADAMW_RIDE_DGELU_PARAMS", dgelu_params);
+        attn = env_int("MB_ADAMW_RIDE_ATTN", attn);
+        attn_blocks = env_int("MB_ADAMW_RIDE_ATTN_BLOCKS", attn_blocks);
+        attn_params = env_long("MB_ADAMW_RIDE_ATTN_PARAMS", attn_params);
+    }
+};
 template <class Take>
 inline int dgrad_with_riders(int dt, int mode, int Mo, int No, int Ko, const void* dY, int ldy, const void* Wt, int ldw, void* dX, int ldx, const void* R,
                              int ldr, float* colsum, DropKey drop, GradAcc acc, hipStream_t st, bool active, const RideOpts& ro, int cus, Take&& take) {
@@ -216,6 +238,16 @@ struct StepMixin {
     bool pkw_enable = false, packed_w = false;
     PrologueArgs::MagPackW pkw = {};
     size_t pk_vis = 0, pk_aco = 0; int pk_Vp = 0, pk_Ap = 0, pk_dtype = 0;
+    // the switches both engines share through this mixin, read once by mb_*_create before the layout is built (which carves the
+    // deterministic shadow).  MB_PROLOGUE_PACK=0: the step prologue stages the fp32 modality tensors and the forward packs them (two
+    // more launches); the other four are described at their fields below
+    void read_env() {
+        ow_enable = env_int("MB_WGRAD_OVERWRITE", ow_enable);
+        keep_enable = env_int("MB_ADAMW_KEEP", keep_enable);
+        deterministic = env_int("MB_DETERMINISTIC", deterministic);
+        pk_enable = env_on("MB_PROLOGUE_PACK", true);
+        pkw_enable = env_on("MB_PROLOGUE_PACKW", true);
+    }
     // single-call step: the prologue counts the occurrences of every token id (workspace offset of the table, 0 = none); `counted`
     // tells the engine's backward that the table describes the batch of this step
     size_t idcnt_off = 0; bool idcnt_enable = false, counted = false;

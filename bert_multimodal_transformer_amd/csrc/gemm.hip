@@ -595,14 +595,49 @@ int gemm_env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
 }
-static int env_int(const char* name, int dflt) { return gemm_env_int(name, dflt); }
-// MB_GEMM_LOG=1: one stderr line per GEMM launch -- kernel symbol (as a kernel trace prints it), number of problems, launch FLOPs and
-// the first problem's M N K -- so that a profile's per-symbol durations can be priced against what the symbol actually computed
-// (bench.py's in-run trace: a captured step logs each of its launches once)
-static int g_gemm_log = -1;
+// The host switches of this file: read once, by the first launch (or query) that looks at one.
+struct HostEnv {
+    // MB_GEMM_LOG=1: one stderr line per GEMM launch -- kernel symbol (as a kernel trace prints it), number of problems, launch FLOPs and
+    // the first problem's M N K -- so that a profile's per-symbol durations can be priced against what the symbol actually computed
+    // (bench.py's in-run trace: a captured step logs each of its launches once)
+    int log;
+    int trace;                   // MB_GEMM_TRACE=1: phase stamps of every block (the device buffer is allocated by the first traced launch)
+    int impl, stages, dbg;       // MB_GEMM_IMPL: 0 auto, 1 = register-staged v1, 2 = LDS-DMA v2 ; MB_GEMM_STAGES: 2|3|4 ; MB_GEMM_DBG: GemmArgs::dbg
+    int ksplit;                  // MB_GEMM_KSPLIT: 1 = k-split waves for the 64 x 64 bf16 tiles (rounds 2-3), 0 (default) = quarter tiles
+    int stages64;                // MB_GEMM_64_STAGES: ring slots of the 64 x 64 quarter-tile kernel (launch_cfg)
+    int tile_n768;               // MB_GEMM_TILE_N768: tile code for auto-selected narrow GEMMs (12872 | 64 | 12864 | 128)
+    int tile_big;                // MB_GEMM_TILE_BIG: 1 = 256 x 128 eight-wave tiles where they make ONE round on the chip (default 0: measured slower)
+    int pn_max, pn_min;          // MB_GEMM_PN_MAX / _MIN (measurement switches): the largest / smallest padded tile count pn_cfg's auto selection takes
+    int pt_on;                   // MB_GEMM_PT=0: no 256 x 64 form in the auto selection
+    int dgelu_rounds;            // MB_ADAMW_RIDE_DGELU_ROUNDS=1: riders in a 128 x 128 dgrad of more than one round (nn_ride_cfg)
+    int group_map;               // MB_GROUP_MAP=0: round-1 placement (eight XCD regions inside every problem)
+    int group_stages;            // MB_GROUP_STAGES: ring of the grouped kernel: 2 | 3 stages of 128-byte k rows, 24 | 25 = 4 | 5 stages of 64-byte k rows
+    int group_big;               // MB_GROUP_BIG: 1 = one wave per SIMD (4 waves, 128 x 64 wave tiles), 2 = 8-wave ping-pong (gemm_pp.hip)
+};
+static HostEnv read_host_env() {
+    HostEnv e;
+    e.log = gemm_env_int("MB_GEMM_LOG", 0);
+    e.trace = gemm_env_int("MB_GEMM_TRACE", 0);
+    e.impl = gemm_env_int("MB_GEMM_IMPL", 0); e.stages = gemm_env_int("MB_GEMM_STAGES", 0); e.dbg = gemm_env_int("MB_GEMM_DBG", 0);
+    e.ksplit = gemm_env_int("MB_GEMM_KSPLIT", 0);
+    e.stages64 = gemm_env_int("MB_GEMM_64_STAGES", 3);
+    e.tile_n768 = gemm_env_int("MB_GEMM_TILE_N768", 12872);
+    e.tile_big = gemm_env_int("MB_GEMM_TILE_BIG", 0);
+    e.pn_max = gemm_env_int("MB_GEMM_PN_MAX", 256); e.pn_min = gemm_env_int("MB_GEMM_PN_MIN", 168);
+    e.pt_on = gemm_env_int("MB_GEMM_PT", 1);
+    e.dgelu_rounds = gemm_env_int("MB_ADAMW_RIDE_DGELU_ROUNDS", 0);
+    e.group_map = gemm_env_int("MB_GROUP_MAP", 1);
+    e.group_stages = gemm_env_int("MB_GROUP_STAGES", 2);
+    e.group_big = gemm_env_int("MB_GROUP_BIG", 2);
+    return e;
+}
+static const HostEnv& host_env() {
+    static const HostEnv e = read_host_env();
+    return e;
+}
+
 void gemm_log(const void* fn, hipStream_t st, const GemmArgs* p, int count) {
-    if (g_gemm_log < 0) g_gemm_log = env_int("MB_GEMM_LOG", 0);
-    if (!g_gemm_log) return;
+    if (!host_env().log) return;
     double fl = 0.0;
     for (int i = 0; i < count; ++i) fl += 2.0 * (double)p[i].M * (double)p[i].N * (double)p[i].K;
     const char* name = hipKernelNameRefByPtr(fn, st);
@@ -610,20 +645,21 @@ void gemm_log(const void* fn, hipStream_t st, const GemmArgs* p, int count) {
 }
 
 void gemm_log_ride(const AdamRide& r) {
-    if (g_gemm_log < 0) g_gemm_log = env_int("MB_GEMM_LOG", 0);
-    if (g_gemm_log && r.blocks > 0 && r.n4 > 0) fprintf(stderr, "[magbert ride] params=%zu blocks=%d\n", r.n4 * 4, r.blocks);      // (not the touch-only riders)
+    if (host_env().log && r.blocks > 0 && r.n4 > 0) fprintf(stderr, "[magbert ride] params=%zu blocks=%d\n", r.n4 * 4, r.blocks);      // (not the touch-only riders)
 }
 
 static unsigned long long* g_trace = nullptr;       // MB_GEMM_TRACE=1: device buffer of phase stamps, [kTraceBlocks][8]
-static int g_trace_on = -1, g_trace_blocks = 0;
+static int g_trace_blocks = 0;
+static bool g_trace_failed = false;                 // (the buffer could not be allocated: no stamps)
 constexpr int kTraceBlocks = 8192 * 8 / kTraceStride;
+// -> the cleared stamp buffer of a launch of `blocks` blocks, null when tracing is off (or the launch is too large for it)
 static unsigned long long* trace_buffer(int blocks, hipStream_t st) {
-    if (g_trace_on < 0) {
-        const char* v = getenv("MB_GEMM_TRACE");
-        g_trace_on = v ? atoi(v) : 0;
-        if (g_trace_on && hipMalloc(&g_trace, (size_t)kTraceBlocks * kTraceStride * sizeof(unsigned long long)) != hipSuccess) g_trace_on = 0;
+    if (!host_env().trace || g_trace_failed) return nullptr;
+    if (!g_trace && hipMalloc(&g_trace, (size_t)kTraceBlocks * kTraceStride * sizeof(unsigned long long)) != hipSuccess) {
+        g_trace = nullptr; g_trace_failed = true;
+        return nullptr;
     }
-    if (!g_trace_on || blocks > kTraceBlocks) return nullptr;
+    if (blocks > kTraceBlocks) return nullptr;
     g_trace_blocks = blocks;
     (void)hipMemsetAsync(g_trace, 0, (size_t)blocks * kTraceStride * sizeof(unsigned long long), st);
     return g_trace;
@@ -635,16 +671,9 @@ int gemm_trace_fetch(unsigned long long* host_out, int max_blocks) {
     if (hipMemcpy(host_out, g_trace, (size_t)n * kTraceStride * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     return n;        // (a -DMB_GEMM_LOOPTRACE build hands out kTraceStride = 128 u64 per block: the caller sizes host_out for that)
 }
-unsigned long long* gemm_trace_buffer(int blocks, hipStream_t st) {
-    if (g_trace_on == 0) return nullptr;
-    return trace_buffer(blocks, st);
-}
-static int g_impl = -1, g_stages = -1, g_dbg = 0;      // MB_GEMM_IMPL: 0 auto, 1 = register-staged v1, 2 = LDS-DMA v2 ; MB_GEMM_STAGES: 2|3|4
+unsigned long long* gemm_trace_buffer(int blocks, hipStream_t st) { return trace_buffer(blocks, st); }
 
-int gemm_dbg_flags() {
-    if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
-    return g_dbg;
-}
+int gemm_dbg_flags() { return host_env().dbg; }
 
 // choose the 8-region (one per XCD) decomposition with the smallest per-XCD panel footprint; returns the padded grid size
 template <int BM, int BN>
@@ -672,14 +701,14 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t st) {
     splits = (p.K + kchunk - 1) / kchunk;
     p.kchunk = kchunk;
     dim3 grid(tiles, splits);
-    if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
-    p.dbg = g_dbg;
-    p.trace = (g_trace_on != 0) ? trace_buffer(tiles * splits, st) : nullptr;
+    const HostEnv& env = host_env();
+    p.dbg = env.dbg;
+    p.trace = trace_buffer(tiles * splits, st);
     // v2 preconditions (see the kernel header)
     bool v2ok = (p.K % BKE == 0) && (p.lda % EPV == 0) && (p.ldb % EPV == 0) && (((uintptr_t)p.A | (uintptr_t)p.B) % 16 == 0);
     if (AK) v2ok = v2ok && (p.M % BM == 0);
     if (BK) v2ok = v2ok && (p.N % BN == 0);
-    if (g_impl == 1) v2ok = false;
+    if (env.impl == 1) v2ok = false;
     if (p.bseg > 0) {          // segmented B: LDS-DMA kernels only, whole tiles / k-stages per segment, no split-K
         if (splits != 1 || (BK ? (p.bseg % BN != 0) : (p.bseg % 128 != 0)) || p.bseg_stride % EPV || !v2ok) return MB_ERR_SHAPE;
     }
@@ -696,19 +725,17 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t st) {
     if (v2ok) {
         // (KB, NSTAGE) per tile: MB_GEMM_STAGES = 10*KBsel + stages overrides (KBsel 1 -> 128-byte rows, 2 -> 64-byte rows)
         int ns = 2, kb = 128;      // measured best (per-layer GEMM 290 us): deeper rings / 64-byte rows do not pay
-        if (g_stages > 0) { kb = (g_stages / 10 == 2) ? 64 : 128; ns = g_stages % 10; }
+        if (env.stages > 0) { kb = (env.stages / 10 == 2) ? 64 : 128; ns = env.stages % 10; }
         if (kb == 64 && (p.kchunk % (64 / (int)sizeof(T)) != 0)) kb = 128;
         // the two-slot bf16 loop is a software pipeline with its last two stages peeled: a k range of a single stage takes the
         // three-slot kernel (plain loop)
         if (sizeof(T) == 2 && ns <= 2 && p.kchunk / (kb / (int)sizeof(T)) < 2) ns = 3;
 #define MB_LAUNCH2(NS, KBV) MB_GEMM_LAUNCH((gemm2_kernel<T, BM, BN, AK, BK, MODE, NS, KBV>), grid, dim3(256), st, p, &p, 1)
-        static int g_ks = -1;             // MB_GEMM_KSPLIT: 1 = k-split waves for the 64 x 64 bf16 tiles (rounds 2-3), 0 (default) = quarter tiles
-        if (g_ks < 0) g_ks = env_int("MB_GEMM_KSPLIT", 0);
         if constexpr (BM == 64 && BN == 64 && sizeof(T) == 2) {
             // each k-split block holds 64 KB of LDS (2 per CU): worth it while the whole grid is co-resident and the k loop is long
             // enough to amortise the four-tile epilogue (K = 768: 3 stages, measured 10.8 vs 9.8 us); beyond that
             // (T = 4096: 768 tiles) the 32 KB quarter-tile kernel's higher residency wins (measured: 7.30 vs 7.97 ms per step)
-            if (g_ks && g_stages <= 0 && p.kchunk % 128 == 0 && p.kchunk >= 1024 && splits == 1 && tiles <= 512) {
+            if (env.ksplit && env.stages <= 0 && p.kchunk % 128 == 0 && p.kchunk >= 1024 && splits == 1 && tiles <= 512) {
                 MB_GEMM_LAUNCH((gemm2_kernel<T, BM, BN, AK, BK, MODE, 2, 256, true>), grid, dim3(256), st, p, &p, 1);
                 return (int)hipGetLastError();
             }
@@ -718,9 +745,7 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t st) {
             // Same box, ms per step (profiles/r04_gemm64_ring_ab.txt): k-split + 2 slots 3.648 | k-split + 3 slots 3.62 | 3 slots
             // everywhere 3.60 | 4 slots everywhere 3.64; MAG-XLNet 4.25 -> 4.19.  Not beyond 512 tiles: at T = 4096 (768 tiles) the
             // two-slot kernel's five blocks per CU win (5.14 vs 5.19 ms).  MB_GEMM_64_STAGES=0 MB_GEMM_KSPLIT=1: the round-3 selection.
-            static int g_64st = -1;
-            if (g_64st < 0) g_64st = env_int("MB_GEMM_64_STAGES", 3);
-            if (g_64st >= 3 && g_stages <= 0 && splits == 1 && p.kchunk / BKE >= 2 && tiles <= 512) ns = g_64st > 4 ? 4 : g_64st;
+            if (env.stages64 >= 3 && env.stages <= 0 && splits == 1 && p.kchunk / BKE >= 2 && tiles <= 512) ns = env.stages64 > 4 ? 4 : env.stages64;
         }
         if (kb == 128) {
             if (BM == 128) { if (ns <= 2) MB_LAUNCH2(2, 128); else if (ns == 3) MB_LAUNCH2(3, 128); else MB_LAUNCH2(4, 128); }
@@ -740,33 +765,27 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t st) {
 // shorter than three of them, a segmented B, split-K, and (unless the caller named the tile) more than 256 padded tiles -- one tile per
 // CU: a second round costs more than the 64 x 64 kernel's three blocks per CU (T = 4096: 384 tiles) -- or fewer than 168: small problems
 // keep the finer 64 x 64 grid.
-static int g_tile_n768 = -1;       // MB_GEMM_TILE_N768: tile code for auto-selected narrow GEMMs (12872 | 64 | 12864 | 128)
-static int tile_n768() {
-    if (g_tile_n768 < 0) g_tile_n768 = env_int("MB_GEMM_TILE_N768", 12872);
-    return g_tile_n768;
-}
+static int tile_n768() { return host_env().tile_n768; }
 // `tall` in: 1 = only the 256 x 64 form (tile code 25672), 0 = only 128 x 64 (12872), -1 = whichever makes one round (the auto selection:
 // 128 x 64 first; the tall form -- 64-deep stages, K >= 192 -- where that one would need a second round, MB_GEMM_PT=0 turns it off);
 // out: which one it is.
 static int pn_cfg(const GemmArgs& a, bool ak, bool bk, int splits, bool forced, GemmArgs& p, int* tall = nullptr) {
     const int want = tall ? *tall : 0;
     if (tall) *tall = 0;
-    static int pn_max = -1, pn_min = 168, pt_on = -1;         // MB_GEMM_PN_MAX / _MIN (measurement switches): the largest / smallest padded tile count the auto selection takes
-    if (pn_max < 0) { pn_max = env_int("MB_GEMM_PN_MAX", 256); pn_min = env_int("MB_GEMM_PN_MIN", 168); pt_on = env_int("MB_GEMM_PT", 1); }
-    if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
-    const bool common = splits <= 1 && g_impl != 1 && g_stages <= 0 && a.bseg <= 0 && (a.lda % 8 == 0) && (a.ldb % 8 == 0) &&
+    const HostEnv& env = host_env();
+    const bool common = splits <= 1 && env.impl != 1 && env.stages <= 0 && a.bseg <= 0 && (a.lda % 8 == 0) && (a.ldb % 8 == 0) &&
                         (((uintptr_t)a.A | (uintptr_t)a.B) % 16 == 0) && (!bk || a.N % 64 == 0);
     if (!common) return 0;
     for (int form = 0; form < 2; ++form) {
-        if ((want == 0 && form == 1) || (want == 1 && form == 0) || (form == 1 && want < 0 && !pt_on)) continue;
+        if ((want == 0 && form == 1) || (want == 1 && form == 0) || (form == 1 && want < 0 && !env.pt_on)) continue;
         p = a;
         const int tiles = form ? choose_regions<256, 64>(p) : choose_regions<128, 64>(p);
         const int ke = form ? 64 : 128, bm = form ? 256 : 128;
-        bool ok = (p.K % ke == 0) && p.K / ke >= 3 && (forced || (tiles <= pn_max && tiles >= pn_min));
+        bool ok = (p.K % ke == 0) && p.K / ke >= 3 && (forced || (tiles <= env.pn_max && tiles >= env.pn_min));
         if (ak) ok = ok && (p.M % bm == 0);
         if (!ok) continue;
         p.kchunk = p.K;
-        p.dbg = g_dbg;
+        p.dbg = env.dbg;
         p.trace = nullptr;
         if (tall) *tall = form;
         return tiles;
@@ -782,12 +801,10 @@ static int nn_ride_cfg(int mode, const GemmArgs& a, GemmArgs& p, int* per_cu, in
     constexpr int BKE = 64, EPV = 8;
     p = a;
     if (pn) *pn = 0;
-    if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
-    static int plain = -1;          // every selection switch of launch_tile / launch_cfg at its default (else: the plain launch, no riders)
-    if (plain < 0)
-        plain = (env_int("MB_GEMM_TRACE", 0) == 0 && env_int("MB_GEMM_64_STAGES", 3) == 3 &&
-                 env_int("MB_GEMM_KSPLIT", 0) == 0 && (env_int("MB_GEMM_TILE_BIG", 0) & ~4) == 0) ? 1 : 0;
-    if (g_impl == 1 || g_stages > 0 || !plain || a.bseg > 0) return 0;
+    const HostEnv& env = host_env();
+    // every selection switch of launch_tile / launch_cfg at its default (else: the plain launch, no riders)
+    const bool plain = env.trace == 0 && env.stages64 == 3 && env.ksplit == 0 && (env.tile_big & ~4) == 0;
+    if (env.impl == 1 || env.stages > 0 || !plain || a.bseg > 0) return 0;
     if (mode != EPI_ADD_RES && mode != EPI_DGELU) return 0;
     const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
     const bool big = t128 >= 224;
@@ -807,12 +824,10 @@ static int nn_ride_cfg(int mode, const GemmArgs& a, GemmArgs& p, int* per_cu, in
     //  same and simply takes more rounds: at T = 4096 its 768 tiles are one and a half -- riders in the slots its second round leaves free were
     //  measured: 3.7 M parameters stretch the launch from 33 to 47 us, the step gains nothing (4.72 vs 4.72 ms) and loses 0.4 % once the narrow
     //  dgrads carry riders of their own, profiles/r06_c5_dgelu_riders.txt, r06_pt_first_ab.txt; MB_ADAMW_RIDE_DGELU_ROUNDS=1 allows them)
-    static int dgelu_rounds = -1;
-    if (dgelu_rounds < 0) dgelu_rounds = env_int("MB_ADAMW_RIDE_DGELU_ROUNDS", 0);
-    if (tiles > (big && dgelu_rounds ? 4096 : 512)) return 0;
+    if (tiles > (big && env.dgelu_rounds ? 4096 : 512)) return 0;
     if (per_cu) *per_cu = big ? 2 : 3;
     p.kchunk = p.K;
-    p.dbg = g_dbg;
+    p.dbg = env.dbg;
     p.trace = nullptr;
     if (mode == EPI_DGELU && p.colsum == nullptr && p.Cf != nullptr) { p.colsum = p.Cf; p.Cf = nullptr; }      // (as engine_common.h gemm())
     return tiles;
@@ -844,26 +859,25 @@ static int launch_pn(const GemmArgs& a, int splits, bool forced, hipStream_t st,
         GemmArgs p;
         const int tiles = pn_cfg(a, AK, BK, splits, forced, p, &tall);
         if (tiles > 0) {
-            p.trace = (g_trace_on != 0) ? trace_buffer(tiles, st) : nullptr;
+            p.trace = trace_buffer(tiles, st);
             const int rc = gemm_pn_launch(AK, BK, MODE, p, dim3(tiles), st, tall == 1);
             if (rc != MB_ERR_MODE) return rc;      // (a layout / epilogue pair that is not instantiated: 64 x 64)
         }
     }
     return launch_cfg<T, 64, 64, AK, BK, MODE>(a, splits, st);
 }
-static int g_tile_big = -1;        // MB_GEMM_TILE_BIG: 1 = 256 x 128 eight-wave tiles where they make ONE round on the chip (default 0: measured slower)
 
 template <class T, bool AK, bool BK, int MODE>
 static int launch_tile(const GemmArgs& a, int splits, int tile, hipStream_t st) {
     const bool forced = tile != 0;
     if (tile == 0) {   // heuristic: fill >= ~1 wave of the 256 CUs
         const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * (splits < 1 ? 1 : splits);
-        if (g_tile_big < 0) g_tile_big = env_int("MB_GEMM_TILE_BIG", 0);
+        const int big = host_env().tile_big;
         tile = (t128 >= 224) ? 128 : tile_n768();
         // one 256 x 128 tile per CU: taken when the whole output is a single, reasonably full round of the 256 CUs
         const long t256 = (long)((a.M + 255) / 256) * ((a.N + 127) / 128);
         // (2: also when it takes more than one round; 4: the forward launches only -- row x row operands --, the dgrad launches keep their riders)
-        if (g_tile_big && (g_tile_big != 4 || (!AK && !BK)) && sizeof(T) == 2 && splits <= 1 && (t256 <= 256 || g_tile_big == 2) && t256 >= 168) tile = 256;
+        if (big && (big != 4 || (!AK && !BK)) && sizeof(T) == 2 && splits <= 1 && (t256 <= 256 || big == 2) && t256 >= 168) tile = 256;
     }
     if constexpr (sizeof(T) == 2) {
         if (tile == 256) return launch_cfg<T, 256, 128, AK, BK, MODE>(a, splits, st);
@@ -920,8 +934,7 @@ static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int 
         if (ride->blocks % 8 || adam || BM < 128) return MB_ERR_ARG;
         ga.ride = *ride;
     }
-    static int g_map = -1;           // MB_GROUP_MAP=0: round-1 placement (eight XCD regions inside every problem)
-    if (g_map < 0) g_map = env_int("MB_GROUP_MAP", 1);
+    const HostEnv& env = host_env();
     int total = 0;
     for (int i = 0; i < count; ++i) {
         GemmArgs& p = ga.g[i];
@@ -931,7 +944,7 @@ static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int 
             (((uintptr_t)p.A | (uintptr_t)p.B) % 16))
             return MB_ERR_SHAPE;
         ga.first[i] = total;
-        if (g_map) {
+        if (env.group_map) {
             p.tpr_m = p.M / BM; p.tpr_n = p.N / BN;
             p.reg_m = p.tpr_n >= p.tpr_m ? 0 : 1;               // strips run across the longer side
             total += p.tpr_m * p.tpr_n;
@@ -939,34 +952,29 @@ static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int 
             total += choose_regions<BM, BN>(p);
         }
         p.kchunk = p.K;
-        if (g_impl < 0) { g_impl = env_int("MB_GEMM_IMPL", 0); g_stages = env_int("MB_GEMM_STAGES", 0); g_dbg = env_int("MB_GEMM_DBG", 0); }
-        p.dbg = g_dbg;
+        p.dbg = env.dbg;
     }
     ga.first[count] = total;
-    static int g_gstages = -1;       // MB_GROUP_STAGES: ring of the grouped kernel: 2 | 3 stages of 128-byte k rows, 24 | 25 = 4 | 5 stages of 64-byte k rows
-    if (g_gstages < 0) g_gstages = env_int("MB_GROUP_STAGES", 2);
-    ga.chunk = g_map ? (total + 7) / 8 : 0;
-    if (g_map)
+    ga.chunk = env.group_map ? (total + 7) / 8 : 0;
+    if (env.group_map)
         for (int i = 0; i < count; ++i) {       // strip width: one strip ~ one XCD's share (chunk) of the list
             const int shortside = std::min(ga.g[i].tpr_m, ga.g[i].tpr_n);
             ga.g[i].reg_n = std::max(1, (ga.chunk + shortside / 2) / shortside);
         }
-    const int grid = g_map ? 8 * ga.chunk : total;
-    if (g_trace_on != 0) {
+    const int grid = env.group_map ? 8 * ga.chunk : total;
+    if (env.trace) {
         unsigned long long* tr = trace_buffer(grid + ga.ride.blocks, st);
         for (int i = 0; i < count; ++i) ga.g[i].trace = tr;
     }
     if constexpr (BM == 256) {          // 8-wave ping-pong tiles (gemm_pp.hip): one 256 x 128 tile per CU
         if (adam) return MB_ERR_MODE;
         for (int i = 0; i < count; ++i) if (ga.g[i].K / BKE < 3) return MB_ERR_SHAPE;
-        static int g_big = -1;           // MB_GROUP_BIG: 1 = one wave per SIMD (4 waves, 128 x 64 wave tiles), 2 = 8-wave ping-pong (gemm_pp.hip)
-        if (g_big < 0) g_big = env_int("MB_GROUP_BIG", 2);
-        if (g_big == 2) return gemm_pp_grouped_launch(ga, grid, st);
+        if (env.group_big == 2) return gemm_pp_grouped_launch(ga, grid, st);
         gemm_log_ride(ga.ride);
         MB_GEMM_LAUNCH((gemm2_grouped_tn_kernel<T, BM, BN, 2, 128>), dim3(grid + ga.ride.blocks), dim3(256), st, ga, ga.g, count);
         return (int)hipGetLastError();
     } else {
-    int gst = stages > 0 ? stages : g_gstages;       // the caller's choice for THIS group (MAG's small one: below) or the global switch
+    int gst = stages > 0 ? stages : env.group_stages;       // the caller's choice for THIS group (MAG's small one: below) or the global switch
     if (sizeof(T) == 2 && gst == 2 && ga.g[0].K / BKE < 2) gst = 3;      // (all problems of a group share K) single-stage k range: plain loop
     // A group of few 64 x 64 tiles (MAG: 360 tiles for 512 slots, 8 MFMAs per wave and stage) is pure load latency: one k stage
     // costs one memory round trip divided by the stages in flight.  4 | 5 ring slots of 128-byte rows = 64 | 80 KB, still 2 blocks

@@ -1,34 +1,50 @@
 // 256 x 128 bf16 GEMM tile run by EIGHT waves as two staggered four-wave groups ("ping-pong").
 //
-// Same math and the same callers as gemm.hip (the Linear layers under /root/reference/bert.py:221-229 and the weight gradients of
-// loss.backward(), /root/reference/multimodal_driver.py:378); what differs is who is on the matrix pipe when.
+// Same math and the same callers as gemm.hip (the Linear layers of the encoder and the weight gradients of loss.backward()); what
+// differs is who is on the matrix pipe when.
 //
 // Why: two co-resident 128 x 128 blocks per CU need the CU's whole 64 B/clk L2 -> LDS fill path at full MFMA rate and sit at ~50 %
-// of it.  One 256 x 128 tile moves 25 % fewer operand bytes per FLOP -- but eight waves behind ONE barrier issue DMA,
-// read LDS and run MFMA in lockstep: every SIMD's matrix pipe idles while both of its waves read fragments (the round-2 kernel that
-// lost).  Here the workgroup's two halves are offset by one barrier phase:
-//
-//     phase      2t                     2t+1                   2t+2
-//     group 0    LOAD(t)                COMP(t)                LOAD(t+1)
-//     group 1    COMP(t-1)              LOAD(t)                COMP(t)
+// of it.  One 256 x 128 tile moves 25 % fewer operand bytes per FLOP -- but eight waves that issue DMA, read LDS and
+// run MFMA in lockstep leave every SIMD's matrix pipe idle while both of its waves read fragments (the round-2 kernel that lost).
+// Here a k-stage is two phases per wave, and the workgroup's two halves run them in opposite order:
 //
 //   LOAD(t): all fragment reads of k-stage t (64 registers: the wave's 64 x 64 quarter of its group's 128 x 128 half, two 32-deep
 //            slabs) and NOTHING else; nothing for the matrix pipe
 //   COMP(t): 32 MFMAs out of registers, with this wave's 6 DMA pieces of a later stage and the next LOAD's addresses between them
-// A SIMD hosts wave w (group 0) and wave w+4 (group 1): in every phase one of them feeds the matrix pipe while the other feeds the
-// LDS / DMA queues -- the complementary pairing MI355X_MICROARCH.md "Two waves per SIMD" item 5 asks for.  The two groups share the
-// B image (128 columns) and the barrier; group 0 owns tile rows 0-127, group 1 rows 128-255.
 //
-// (That is the two-barrier form the kernel was built in, and the picture the phase names come from.  The default since late round 6 keeps
-//  ONE of the two barriers per stage -- group 0 meets it behind COMP, group 1 behind LOAD; see MB_PP_ONE_BARRIER in the body -- with the
-//  same per-wave instruction order, DMA schedule and waits.  gemm_pn_kernel is the same loop on a 128 x 64 tile with 128 k per stage.)
+// A SIMD hosts wave w (group 0) and wave w+4 (group 1): while one of them feeds the matrix pipe the other feeds the LDS / DMA
+// queues -- the complementary pairing MI355X_MICROARCH.md "Two waves per SIMD" item 5 asks for.  The two groups share the B image
+// (128 columns) and the barrier; group 0 owns tile rows 0-127, group 1 rows 128-255.  gemm_pn_kernel / gemm_pt_kernel are the same
+// loop on a 128 x 64 tile with 128 k per stage and on a 256 x 64 tile with 64 k per stage.
 //
-// Ring: three 48-KB slots.  In COMP(t) group 0 (phase 2t+1) requests its share of stage t+2, group 1 (phase 2t+2) its share of stage
-// t+3 -- into the slot stage t-1 resp. t lived in, whose last reader drained its reads before the barrier in front of that phase
-// (WAR).  Landing (RAW): a wave's pieces of stage t+1 are counted out (s_waitcnt vmcnt) in phase 2t+1 by BOTH groups -- group 0 at the
-// end of COMP(t), group 1 at the end of LOAD(t) -- i.e. before the barrier in front of the first read of stage t+1 (group 0, phase
-// 2t+2); every piece has had at least two phases to land by then.  Both groups run BOTH waits (no branch on the group in the loop):
-// the other one is free for group 0 (nothing younger outstanding) and a phase early for group 1.
+// The schedule.  B(0) is the barrier behind the prologue, B(t+1) the ONE barrier of k-stage t; "interval t" is what runs between
+// B(t) and B(t+1).  Group 0 meets B(t+1) behind its COMP(t), group 1 behind its LOAD(t), so group 1 runs one phase behind:
+//
+//     interval   t                              t+1
+//     group 0    LOAD(t)    COMP(t)   | B(t+1)  LOAD(t+1)  COMP(t+1) | B(t+2)
+//     group 1    COMP(t-1)  LOAD(t)   | B(t+1)  COMP(t)    LOAD(t+1) | B(t+2)
+//
+// Ring: three slots of one stage each (48 KB; 40 KB in the tall form); stage t lives in slot t % 3.  A wave requests its six pieces
+// of a whole stage inside one COMP, never anywhere else in the loop:
+//   group 0 in COMP(t) = interval t     : stage t+2 -> slot (t+2) % 3, where stage t-1 lived
+//   group 1 in COMP(t) = interval t+1   : stage t+3 -> slot  t    % 3, where stage t   lived
+// (the prologue requests stages 0 and 1 for both groups and stage 2 for group 1; the tail, where no stage is left to request, is
+//  described at the loop).
+//   WAR  Every read of stage s is issued in LOAD(s) -- interval s for both groups -- and has returned (lds_wait_all at the end of
+//        LOAD) before its wave arrives at B(s+1).  Group 0 overwrites stage t-1 in interval t, behind B(t); group 1 overwrites stage t
+//        in interval t+1, behind B(t+1).
+//   RAW  Stage t+1 is first read in interval t+1, behind B(t+1).  Its pieces were requested in interval t-1 (group 0: COMP(t-1),
+//        group 1: COMP(t-2)), and each wave counts its own out -- s_waitcnt vmcnt(pieces per stage): only the stage it requested
+//        last, t+2, may still be in flight -- before it arrives at B(t+1): group 0 at the end of COMP(t), group 1 at the end of LOAD(t).
+//        A piece has had at least two phases to land by then.
+// Both groups run BOTH waits, so the loop has no branch on the group around them: group 0's wait behind LOAD(t) is free (nothing
+// younger than stage t+1 is in flight), group 1's behind COMP(t) asks for stage t+2 an interval before it is needed.
+//
+// MB_PP_ONE_BARRIER=0 builds the form the kernel was first written in (scripts/build_variant.py; the A/B oracle of the hazard argument
+// above): a second barrier per stage, met by group 0 behind LOAD and by group 1 behind COMP, so that all eight waves change phase
+// together -- the same per-wave instruction order, DMA schedule and waits.  That pair only forces the alternation, which B(t+1)
+// restores every stage anyway (group 0 leaves it into a LOAD, group 1 into a COMP), and an eight-wave barrier costs ~200 clocks of
+// a ~750-clock phase (profiles/r06_pn_looptrace.txt).
 #include "gemm_tile.h"
 #include "adamw_dev.h"
 
@@ -45,10 +61,6 @@ constexpr int kPpStage = (kPpBM + kPpBN) * kPpKB;       // 48 KB
 // 32-deep slabs: 16 MFMAs and 16 (row image) / 24-32 (k-major) fragment reads per stage.  25 % fewer operand bytes per FLOP than
 // the 64 x 64 tiles those launches run otherwise (they are bound by the L2 -> LDS fill).
 constexpr int kPnBM = 128, kPnBN = 64, kPnKB = 256;
-#ifndef MB_PN_KSW
-#define MB_PN_KSW 0            // 1 = k-split waves in the narrow tile (measured: the loop gains 9 %, the four-partial epilogue takes it back)
-#endif
-constexpr bool kPnKsw = MB_PN_KSW != 0;
 // The tall form for the same launches at T = 4096 (MOSEI shape: 128 x 64 would make 384 tiles = one and a half rounds): 256 x 64 outputs,
 // 64 k per stage -- 40-KB stages, five DMA pieces per wave; a wave owns 64 x 32 outputs and two slabs (16 MFMAs, 12 / 16 reads per
 // stage).  16 x 12 = 192 tiles at T = 4096: one round, and 64 CUs left to the riders.
@@ -65,18 +77,13 @@ constexpr int kPpFirst = 4, kPpIters = 10, kPpPoints = 6;
 // dst = s + v as a pinned statement (stays between the MFMAs it is written between)
 __device__ __forceinline__ void pinned_add(uint32_t& dst, uint32_t s, uint32_t v) { asm volatile("v_add_u32 %0, %1, %2" : "=v"(dst) : "s"(s), "v"(v)); }
 
-// KSW (the narrow tile): the four waves of a group split the STAGE's k range instead of the group's outputs -- wave w multiplies slab w
-// of every stage for the group's whole 64 x 64 half (16 accumulator tiles, partial sums added in the epilogue).  Half the fragment
-// reads per MFMA of the 32 x 32-per-wave split: 8 (12 with a k-major B) instead of 16 (24) per stage, and both phases of the loop were
-// as long as those reads take (profiles/r06_pn_looptrace.txt: COMP 464 clocks for 272 of MFMA next to a partner issuing 16 reads).
-template <int BM, int BN, int KB, bool AK, bool BK, int MODE, bool KSW = false>
+template <int BM, int BN, int KB, bool AK, bool BK, int MODE>
 __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, const int n0, char* smem) {
     typedef bf16 T;
     constexpr int NW = kPpWaves, STAGE = (BM + BN) * KB;
     constexpr int BKE = KB / 2;                    // 64 (128) k per stage
-    static_assert(!KSW || BKE / 32 == 4, "k-split waves: one 32-deep slab per wave and stage");
-    // a wave: 64 x 64 (32 x 32) outputs, two (four) 32-deep slabs per stage; KSW: the group's 64 x 64, one slab
-    constexpr int MT = KSW ? BM / 32 : BM / 64, NT = KSW ? BN / 16 : BN / 32, NSLAB = KSW ? 1 : BKE / 32;
+    // a wave: 64 x 64 (32 x 32) outputs, two (four) 32-deep slabs per stage
+    constexpr int MT = BM / 64, NT = BN / 32, NSLAB = BKE / 32;
     typedef Dma<T, BM, AK, KB, NW> DA;
     typedef Dma<T, BN, BK, KB, NW> DB;
     constexpr int G = DA::NI + DB::NI;             // DMA pieces per wave per stage (4 + 2)
@@ -84,11 +91,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     typedef typename DB::template Reader<NT, NSLAB> RB_;
     constexpr int NRA = MT * RA::READS_PER_FRAG, NRB = NT * RB_::READS_PER_FRAG;
     constexpr int NM = MT * NT * NSLAB;            // MFMAs per stage (32 | 16)
-#ifdef MB_PP_SPREAD
-    constexpr bool SPREAD = MB_PP_SPREAD != 0;     // (A/B builds)
-#else
     constexpr bool SPREAD = NM < 32;               // DMA pieces at even distances over the MFMAs of COMP (else: behind the first MFMAs)
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,22 +114,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // The narrow tile has four accumulator tiles per wave: slab after slab into the same four, an MFMA meets its predecessor on that
-    // tile four issues later.  NACC > 1: the slabs of a stage accumulate into NACC separate sets (summed behind the k loop), 16
-    // independent chains like the 256 x 128 form.
-#ifdef MB_PN_NACC
-    constexpr int NACC = MB_PN_NACC;
-#else
-    constexpr int NACC = 1;        // (measured with 4 sets in the narrow tile: the same loop, profiles/r06_pn_nacc.txt -- the chain is not what COMP waits for)
-#endif
-    static_assert(NSLAB % NACC == 0, "whole slabs per accumulator set");
-    f32x4 accx[NACC > 1 ? NACC - 1 : 1][MT][NT];
-#pragma unroll
-    for (int a = 0; a < (NACC > 1 ? NACC - 1 : 1); ++a)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) accx[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // (the narrow tile has four accumulator tiles per wave: slab after slab into the same four, an MFMA meets its predecessor on that
+    //  tile four issues later -- which is not what its COMP waits for: profiles/r06_pn_nacc.txt)
 
     auto stamp = [&](int k) {
         if (p.trace && tid == 0) p.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kTraceStride + k] = wall_clock64();
@@ -145,13 +134,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     RA ra;
     RB_ rb;
     const uint32_t lds0 = (uint32_t)(size_t)LDS_PTR(smem);
-    if constexpr (KSW) {
-        ra.init(lds0, grp * (BM / 2), wave & 3, lane);
-        rb.init(lds0 + BM * KB, 0, wave & 3, lane);
-    } else {
-        ra.init(lds0, wr * (BM / 4), 0, lane);
-        rb.init(lds0 + BM * KB, wc * (BN / 2), 0, lane);
-    }
+    ra.init(lds0, wr * (BM / 4), 0, lane);
+    rb.init(lds0 + BM * KB, wc * (BN / 2), 0, lane);
     // A wave's pieces of a stage are CONSECUTIVE 1-KB pieces of the image (wave * NI + i): one m0 per operand and stage, piece i is
     // the instruction's immediate offset i * 1024 -- which the hardware adds to the LDS address AND to the memory address, so the
     // lane offsets are taken back by i * 1024 and the descriptors' bases by kBias to keep them non-negative.
@@ -164,22 +148,14 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A - kBias), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)B - kBias), 0, -1, 0x00020000);
     const uint32_t ksa = DA::k_stride_bytes(p.lda) * BKE, ksb = DB::k_stride_bytes(p.ldb) * BKE;      // operand bytes per stage
-    // MB_PP_SPLIT_DMA=1 (experiment): the DMA pieces of a stage are issued in two halves: pieces [0, GA) behind the fragment reads of a
-    // LOAD (the wave waits for LDS there anyway), pieces [GA, G) between the MFMAs of a COMP.  The narrow tile's COMP takes ~440 clocks
-    // for 272 of MFMA whatever sits next to them (six pieces or three, spread or not, one accumulator chain or four, 16 partner reads
-    // or 8: profiles/r06_pn_looptrace.txt, r06_pn_nacc.txt, r06_pn_ksw.txt, r06_pp_split_dma.txt).  GA <= DA::NI: the first half is operand
-    // A only.  soa_a / dslot_a belong to the first half, soa_b / sob / dslot to the second (group 1's second half runs a stage ahead).
+    // (The narrow tile's COMP takes ~440 clocks for 272 of MFMA whatever sits next to them -- six pieces or three, spread or not, one
+    //  accumulator chain or four, 16 partner reads or 8: profiles/r06_pn_looptrace.txt, r06_pn_nacc.txt, r06_pn_ksw.txt,
+    //  r06_pp_split_dma.txt)
 #ifndef MB_PP_ONE_BARRIER
 #define MB_PP_ONE_BARRIER 1
 #endif
-#ifndef MB_PP_SPLIT_DMA
-#define MB_PP_SPLIT_DMA 0      // measured (profiles/r06_pp_split_dma.txt): stand-alone -0.5 .. -1 us per launch, in the step nothing (+0.2 %); off
-#endif
-    constexpr bool ONEB = MB_PP_ONE_BARRIER != 0;   // one barrier per k-stage (below)
-    constexpr int GA = MB_PP_SPLIT_DMA ? G / 2 : 0;
-    static_assert(GA == 0 || ONEB, "the split DMA issue is written for the one-barrier loop");
-    static_assert(GA <= DA::NI, "the LOAD half holds pieces of operand A only");
-    uint32_t soa_a = 0, soa_b = 0, sob = 0;
+    constexpr bool ONEB = MB_PP_ONE_BARRIER != 0;   // one barrier per k-stage (the file header)
+    uint32_t soa = 0, sob = 0;                      // scalar byte offsets of the next stage to request, in k order
 #ifdef MB_GEMM_ABLATE
     const bool no_dma = (p.dbg & 1) != 0, no_reads = (p.dbg & 4) != 0, no_mfma = (p.dbg & 2) != 0;
 #else
@@ -197,25 +173,19 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, PTR, 16, VOFF, SOFF, 3072, 0); } while (0)
         static_assert(DA::NI <= 4 && DB::NI <= 4, "immediate offsets reach 4095");
         if constexpr (I < DA::NI)
-            MB_PP_PIECE(rsa, (__attribute__((address_space(3))) void*)LDS_PTR(smem + slot + wave * (DA::NI * 1024)), (int)va[I], (int)(I < GA ? soa_a : soa_b), I);
+            MB_PP_PIECE(rsa, (__attribute__((address_space(3))) void*)LDS_PTR(smem + slot + wave * (DA::NI * 1024)), (int)va[I], (int)soa, I);
         else
             MB_PP_PIECE(rsb, (__attribute__((address_space(3))) void*)LDS_PTR(smem + slot + BM * KB + wave * (DB::NI * 1024)), (int)vb[I - DA::NI], (int)sob, I - DA::NI);
 #undef MB_PP_PIECE
     };
-    auto dma_advance_a = [&]() { soa_a += ksa; };
-    auto dma_advance = [&]() {                       // (the COMP half)
-        soa_b += ksa; sob += ksb;
+    auto dma_advance = [&]() {
+        soa += ksa; sob += ksb;
         if (seg_stages > 0 && --seg_left == 0) { sob += seg_extra; seg_left = seg_stages; }
     };
-    auto issue_half_a = [&](uint32_t slot) {
-        static_for<GA>([&](auto ic) { dma_piece(ic, slot); });
-        dma_advance_a();
-    };
-    auto issue_half_b = [&](uint32_t slot) {
-        static_for<G - GA>([&](auto ic) { dma_piece(std::integral_constant<int, GA + decltype(ic)::value>{}, slot); });
+    auto issue_stage = [&](uint32_t slot) {          // this wave's G pieces of the next stage, back to back (prologue and tail)
+        static_for<G>([&](auto ic) { dma_piece(ic, slot); });
         dma_advance();
     };
-    auto issue_stage = [&](uint32_t slot) { issue_half_a(slot); issue_half_b(slot); };
     // An instruction of the wave that is NOT on the matrix pipe costs a whole MFMA time (~16 clocks) while its SIMD partner issues
     // MFMAs back to back, and ~4 clocks inside the MFMA stream itself (tools/mfma_lds_probe, profiles/r06_mfma_lds_probe.txt): so LOAD
     // holds the fragment reads and nothing else -- their addresses are computed in the COMP phase before (addr_*), the DMA pieces
@@ -238,8 +208,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     constexpr int NADDR = RA::NB + RB_::NB;
     auto comp_stage_ = [&](auto dmac, auto mfc, uint32_t slot, uint32_t nxt) {
         constexpr bool DMA = decltype(dmac)::value, MF = decltype(mfc)::value;
-        constexpr int GB = G - GA;                  // pieces of this phase
-        constexpr int NF = (DMA ? GB : 0) + NADDR;
+        constexpr int NF = (DMA ? G : 0) + NADDR;
         auto addr_add = [&](auto jc) {
             constexpr int J = decltype(jc)::value;
             if constexpr (J < RA::NB) pinned_add(addr_a[J], nxt, ra.base[J]);
@@ -247,24 +216,21 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
         };
         static_for<NM>([&](auto mc) {
             constexpr int M = decltype(mc)::value, S = M / (MT * NT), Q = M % (MT * NT);
-            if constexpr (MF) {
-                if constexpr (S % NACC == 0) mma16_pinned(acc[Q / NT][Q % NT], fb[S][Q % NT].v, fa[S][Q / NT].v);
-                else mma16_pinned(accx[S % NACC - 1][Q / NT][Q % NT], fb[S][Q % NT].v, fa[S][Q / NT].v);
-            }
+            if constexpr (MF) mma16_pinned(acc[Q / NT][Q % NT], fb[S][Q % NT].v, fa[S][Q / NT].v);
             if constexpr (SPREAD) {
                 // the narrow tile has 16 MFMAs for the same six pieces: one behind (almost) every MFMA, each piece held the wave's issue for
                 // ~30 clocks (COMP 464 clocks for 272 of MFMA, profiles/r06_pn_looptrace.txt) -- a piece every ~2.7 MFMAs is what the
                 // 256 x 128 form has and pays nothing for
-                constexpr int d0 = DMA ? (M * GB + NM - 1) / NM : 0, d1 = DMA ? ((M + 1) * GB + NM - 1) / NM : 0;
-                static_for<d1 - d0>([&](auto fc) { dma_piece(std::integral_constant<int, GA + d0 + decltype(fc)::value>{}, slot); });
+                constexpr int d0 = DMA ? (M * G + NM - 1) / NM : 0, d1 = DMA ? ((M + 1) * G + NM - 1) / NM : 0;
+                static_for<d1 - d0>([&](auto fc) { dma_piece(std::integral_constant<int, d0 + decltype(fc)::value>{}, slot); });
                 constexpr int a0 = M * NADDR / NM, a1 = (M + 1) * NADDR / NM;
                 static_for<a1 - a0>([&](auto fc) { addr_add(std::integral_constant<int, a0 + decltype(fc)::value>{}); });
             } else {
                 constexpr int f0 = M * NF / NM, f1 = (M + 1) * NF / NM;
                 static_for<f1 - f0>([&](auto fc) {
                     constexpr int F = f0 + decltype(fc)::value;
-                    if constexpr (DMA && F < GB) dma_piece(std::integral_constant<int, GA + F>{}, slot);
-                    else addr_add(std::integral_constant<int, F - (DMA ? GB : 0)>{});
+                    if constexpr (DMA && F < G) dma_piece(std::integral_constant<int, F>{}, slot);
+                    else addr_add(std::integral_constant<int, F - (DMA ? G : 0)>{});
                 });
             }
         });
@@ -285,53 +251,48 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
         else if constexpr (W == 0) wait_vmcnt<0>();
     };
 
-    // Group 0 requests stage t+2 during COMP(t) (phase 2t+1), group 1 stage t+3 during ITS COMP(t) (phase 2t+2): the slot is the
-    // one stage t lived in, which both groups have read by then.  Either way a wave's pieces have >= 2 phases to land.
+    // Prologue: stages 0 and 1 for everybody; group 1, whose first COMP comes an interval late, also requests stage 2 here (group 0
+    // requests it in COMP(0)).  Then stage 0 is counted out: everything but the one (group 1: two) stages requested behind it.
     issue_stage(0u);
     issue_stage((uint32_t)STAGE);
-    if (grp) { issue_half_b(2u * STAGE); wait_vmcnt<2 * G - GA>(); } else wait_vmcnt<G>();      // (group 1's COMP half runs a stage ahead)
-    __builtin_amdgcn_s_barrier();                    // stage 0 has landed for everybody
+    if (grp) { issue_stage(2u * STAGE); wait_vmcnt<2 * G>(); } else wait_vmcnt<G>();
+    __builtin_amdgcn_s_barrier();                    // B(0): stage 0 has landed for everybody
     stamp(1);
-    // ONE barrier per k-stage (MB_PP_ONE_BARRIER, default): group 0 meets it behind its COMP, group 1 behind its LOAD -- the pair that
-    // carries the ring's hazards (a wave's share of stage t+1 has landed; the slot the next DMA pieces go to has been read by everybody).
-    // The other pair of the two-barrier form (group 0 behind LOAD, group 1 behind COMP) only forced the alternation, which the first pair
-    // restores every stage anyway: group 0 leaves it into a LOAD, group 1 into a COMP.  An eight-wave barrier costs ~200 clocks of a
-    // ~750-clock phase (profiles/r06_pn_looptrace.txt).
     if (!ONEB && grp) __builtin_amdgcn_s_barrier();  // (two-barrier form) group 1 runs one phase behind
-    uint32_t cur = 0u, dslot = grp ? 0u : 2u * STAGE, dslot_a = 2u * STAGE;
-    // DM: 1 = every wave requests its next stage between the MFMAs, 2 = group 0 only (in front of the MFMAs), 0 = nobody
+    // cur: the slot LOAD(t) reads, t % 3.  dslot: the slot this wave's next request goes to -- group 0: (t+2) % 3, group 1: (t+3) % 3.
+    uint32_t cur = 0u, dslot = grp ? 0u : 2u * STAGE;
+    // One k-stage of one wave: LOAD(t), COMP(t), and the barrier between them (group 1) or behind them (group 0).
+    // DM: who requests a stage in this COMP -- 1 = every wave, between the MFMAs (the loop) | 2 = group 0 only, in front of the MFMAs (stage
+    //     nt-3: group 0 requests the last stage, nt-1; group 1 did in its COMP(nt-4), or in the prologue) | 0 = nobody (nothing is left)
+    // wc_: what `land` waits for -- W1 = all but the stage requested last | W0 = everything (stage nt-2: the last stage lands) | WN = nothing
     auto stage = [&](int t, auto dm, auto wc_) {
         constexpr int DM = decltype(dm)::value;
         (void)t;
-        // ---- LOAD(t)
+        // ---- LOAD(t): the reads of slot `cur`, returned before the wave goes on (WAR: its next barrier frees the slot)
         PP_LT(t, 0);
         read_stage();
-        if constexpr (GA > 0 && DM != 0) issue_half_a(dslot_a);      // stage t+2, first half (both groups)
         PP_LT(t, 1);
         lds_wait_all();
-        if constexpr (ONEB && GA > 0) { if (grp) land(wc_); }        // (group 0 has stage t+1 AND the half just issued in flight: no wait here)
-        else land(wc_);                              // group 1: its share of stage t+1 has landed (group 0: nothing younger than stage t+1 yet)
+        land(wc_);                                   // RAW, group 1: its share of stage t+1 has landed (group 0: nothing younger than stage t+1 yet)
         PP_LT(t, 2);
         __builtin_amdgcn_sched_barrier(0);           // the scalar bookkeeping of COMP stays behind the barrier (in LOAD it would cost ~16 clocks each)
-        if (!ONEB || grp) __builtin_amdgcn_s_barrier();
+        if (!ONEB || grp) __builtin_amdgcn_s_barrier();      // group 1: B(t+1)
         __builtin_amdgcn_sched_barrier(0);
         PP_LT(t, 3);
-        // ---- COMP(t)
+        // ---- COMP(t): the MFMAs, with the request of stage t+2 (group 0) / t+3 (group 1) into `dslot` between them
         const uint32_t nxt = cur == 2u * STAGE ? 0u : cur + STAGE;
-        if constexpr (DM == 2) { if (!grp) issue_half_b(dslot); }
+        if constexpr (DM == 2) { if (!grp) issue_stage(dslot); }
         // the multiplying wave outranks its SIMD partner's reads: by age alone the older wave (group 0) wins BOTH ways and group 1's
         // 32 MFMAs take ~930 clocks instead of ~510 (profiles/r06_pp_looptrace.txt)
         if (!(p.dbg & 16)) __builtin_amdgcn_s_setprio(1);
         comp_stage(std::integral_constant<bool, DM == 1>{}, dslot, nxt);
         if (!(p.dbg & 16)) __builtin_amdgcn_s_setprio(0);
         PP_LT(t, 4);
-        if constexpr (ONEB && GA > 0) { if (!grp) land(wc_); }
-        else land(wc_);                              // group 0: its share of stage t+1 (group 1: of stage t+2, a phase early -- it has had two)
+        land(wc_);                                   // RAW, group 0: its share of stage t+1 has landed (group 1: of stage t+2, an interval early)
         PP_LT(t, 5);
-        if (!ONEB || !grp) __builtin_amdgcn_s_barrier();
+        if (!ONEB || !grp) __builtin_amdgcn_s_barrier();     // group 0: B(t+1)
         cur = nxt;
         dslot = dslot == 2u * STAGE ? 0u : dslot + STAGE;
-        dslot_a = dslot_a == 2u * STAGE ? 0u : dslot_a + STAGE;
     };
     typedef std::integral_constant<int, 0> D0;
     typedef std::integral_constant<int, 1> D1;
@@ -342,17 +303,8 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& p, const int m0, co
     stage(t + 1, D0{}, W0{});
     stage(t + 2, D0{}, WN{});
     if (!ONEB && !grp) __builtin_amdgcn_s_barrier(); // (two-barrier form) pairs with group 1's last COMP
-    if constexpr (NACC > 1) {
-#pragma unroll
-        for (int a = 0; a < NACC - 1; ++a)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] += accx[a][i][j];
-    }
     stamp(2);
-    if constexpr (KSW) gemm_epilogue<T, BM, BN, MODE, true, NW, 2>(p, acc, m0, n0, wave, lane, smem, pre);
-    else gemm_epilogue<T, BM, BN, MODE, false, NW>(p, acc, m0, n0, wave, lane, smem, pre);
+    gemm_epilogue<T, BM, BN, MODE, false, NW>(p, acc, m0, n0, wave, lane, smem, pre);
     if (p.trace) {
         stamp(3);
         wait_vmcnt<0>();
@@ -380,7 +332,7 @@ __global__ void __launch_bounds__(512) gemm_pn_kernel(const GemmArgs p) {
     __shared__ __attribute__((aligned(1024))) char smem[kPpSlots * kPpStage];
     int m0, n0;
     if (!tile_origin<kPnBM, kPnBN>(p, m0, n0, blockIdx.x)) return;
-    gemm_pp_body<kPnBM, kPnBN, kPnKB, AK, BK, MODE, kPnKsw>(p, m0, n0, smem);
+    gemm_pp_body<kPnBM, kPnBN, kPnKB, AK, BK, MODE>(p, m0, n0, smem);
 }
 
 // a narrow dgrad launch (dX = dY W + R) with riders: 228 tiles at T = 2400 leave whole CUs idle (16 once the grid's padding is counted
@@ -393,7 +345,7 @@ __global__ void __launch_bounds__(512) gemm_pn_ride_kernel(const GemmArgs p, con
     }
     int m0, n0;
     if (!tile_origin<kPnBM, kPnBN>(p, m0, n0, (int)blockIdx.x - ride.blocks)) return;
-    gemm_pp_body<kPnBM, kPnBN, kPnKB, false, true, EPI_ADD_RES, kPnKsw>(p, m0, n0, smem);
+    gemm_pp_body<kPnBM, kPnBN, kPnKB, false, true, EPI_ADD_RES>(p, m0, n0, smem);
 }
 
 template <bool AK, bool BK, int MODE>

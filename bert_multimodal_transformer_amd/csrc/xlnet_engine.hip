@@ -32,7 +32,7 @@ struct mb_xlnet_engine : StepMixin {
     size_t ws_mag, ws_magout, ws_pos, ws_xs, ws_head_z, ws_head_pooled;
     std::vector<size_t> ws_x;
     std::vector<XlLayerWs> lw;
-    size_t ws_dsa[2], ws_dzda[2], ws_dsb[2], ws_dzdb[2], ws_du[2], ws_dqkv[2], ws_dkr[2];   // dY operands of the weight gradients: ping-pong by layer parity
+    size_t ws_dsa[2], ws_dzda[2], ws_dsb[2], ws_dzdb[2], ws_du[2], ws_dqkv[2], ws_dkr[2];   // dY operands of the weight gradients: ping-pong by layer parity (as engine.hip)
     size_t ws_dxa, ws_dxb, ws_dvec, ws_gsave, ws_dz, ws_dxs, ws_lnp_a, ws_lnp_b;
     size_t ws_pdsave = 0;          // max_seq > 128: the tiled backward's second shared scratch plane (dropped probabilities)
     bool tiled() const { return c.max_seq > 128; }
@@ -56,18 +56,9 @@ struct mb_xlnet_engine : StepMixin {
     int B = 0, L = 0, training = 0, padT = -1;
     int group_wgrad = 256;         // MB_GROUP_WGRAD: tile of the per-layer grouped weight-gradient launch (64 | 128 | 256 = 256 x 128 ping-pong), 0 = one by one
                                    // (256 since the ping-pong loop has one barrier per stage: 3.895 -> 3.872 ms, profiles/r06_ride_budget3.txt; fp32 / odd widths: 128)
-    // MB_OVERLAP_WGRAD=1: the grouped launch of layer l runs on an internal side stream under the dgrad chain of layer l-1 (round-1
-    // default; measured equal to the in-line launch on the MAG-BERT engine, which keeps the step one in-order, graph-friendly sequence)
-    int overlap_wgrad = 0;
-    bool deferred = false;
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> evs;   // [2 * n_layer]: fork, done
     // AdamW riders (kernels.h AdamRide; as engine.hip).  This engine's grouped weight gradient fills the chip (504 tiles in 512 slots), so
     // the hosts are the ffn1 / ffn2 / out dgrad launches and the relative-attention backward: MB_ADAMW_RIDE=0 turns them off
-    int adam_ride = 1;
     RideOpts ride_opts;
-    int ride_attn = 1, ride_attn_blocks = 0;
-    long ride_attn_params = 0;
     float* ride_m = nullptr; float* ride_v = nullptr;
     size_t ride_cursor = 0;
     bool ws_zeroed = false;
@@ -159,13 +150,7 @@ static void xl_build_layout(mb_xlnet_engine* e) {
     Carver w;
     e->mw.init(c.dtype, (int)T, (int)H, (int)V, (int)A);
     e->ws_mag = w.take(e->mw.bytes);
-    {   // MB_PROLOGUE_PACK=0: the step prologue stages the fp32 modality tensors and the forward packs them (two more launches)
-        const char* pv = getenv("MB_PROLOGUE_PACK");
-        e->pk_enable = !(pv && atoi(pv) == 0);
-        e->pk_vis = e->ws_mag + e->mw.vp; e->pk_aco = e->ws_mag + e->mw.ap; e->pk_Vp = e->mw.Vp; e->pk_Ap = e->mw.Ap; e->pk_dtype = c.dtype;
-        const char* pw = getenv("MB_PROLOGUE_PACKW");
-        e->pkw_enable = !(pw && atoi(pw) == 0);
-    }
+    e->pk_vis = e->ws_mag + e->mw.vp; e->pk_aco = e->ws_mag + e->mw.ap; e->pk_Vp = e->mw.Vp; e->pk_Ap = e->mw.Ap; e->pk_dtype = c.dtype;
     e->ws_magout = w.take(T * H * es);
     e->ws_pos = w.take(R * H * es);
     e->ws_x.resize(c.n_layer + 1);
@@ -211,8 +196,6 @@ static void xl_build_layout(mb_xlnet_engine* e) {
 
 // state the next pass relies on but that is not part of the pass itself (kept out of captured step graphs)
 static int xl_prepare_pass(mb_xlnet_engine* e, int T, hipStream_t st) {
-    if (e->deferred && e->side)      // a backward that was not run to its last stage may still have weight-gradient GEMMs in flight
-        for (size_t l = 0; l < 2 && 2 * l + 1 < e->evs.size(); ++l) CK((int)hipStreamWaitEvent(st, e->evs[2 * l + 1], 0));
     if (!e->ws_zeroed) { CK((int)hipMemsetAsync(e->ws, 0, e->ws_bytes, st)); e->ws_zeroed = true; e->padT = T; }
     if (e->padT != T) {
         // another batch shape ran before: the pad rows [T, Tp) / [2T, Rp) of every buffer a weight gradient reads as its k-major
@@ -246,28 +229,16 @@ int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out) {
     if (cfg->injection_index < 0 || cfg->injection_index >= cfg->n_layer) return MB_ERR_ARG;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
     mb_xlnet_engine* e = new mb_xlnet_engine();
-    if (const char* v = getenv("MB_GROUP_WGRAD")) e->group_wgrad = atoi(v);
-    if (e->group_wgrad == 256 && (cfg->dtype != DT_BF16 || cfg->d_model % 256 != 0 || cfg->d_inner % 256 != 0)) e->group_wgrad = 128;     // 256 x 128 ping-pong tile: bf16, whole tiles
-    if (const char* v = getenv("MB_OVERLAP_WGRAD")) e->overlap_wgrad = atoi(v);
-    if (const char* v = getenv("MB_WGRAD_OVERWRITE")) e->ow_enable = atoi(v);
-    e->deferred = e->overlap_wgrad && (e->group_wgrad == 64 || e->group_wgrad == 128 || e->group_wgrad == 256) && cfg->d_inner % e->group_wgrad == 0 &&
-                  cfg->d_model % e->group_wgrad == 0;
     e->c = *cfg;
-    if (const char* v = getenv("MB_DETERMINISTIC")) e->deterministic = atoi(v);
+    e->read_env();
+    e->ride_opts.read_env();
+    e->group_wgrad = env_int("MB_GROUP_WGRAD", e->group_wgrad);
+    if (e->group_wgrad == 256 && (cfg->dtype != DT_BF16 || cfg->d_model % 256 != 0 || cfg->d_inner % 256 != 0)) e->group_wgrad = 128;     // 256 x 128 ping-pong tile: bf16, whole tiles
+    e->fuse_qkv = env_on("MB_XL_FUSE_QKV", e->fuse_qkv);
+    e->split_r = env_on("MB_XL_SPLIT_R", e->split_r != 0);
+    e->prefetch = env_int("MB_PREFETCH", e->prefetch);
     xl_build_layout(e);
-    if (const char* v = getenv("MB_XL_FUSE_QKV")) e->fuse_qkv = atoi(v) != 0;
-    if (const char* v = getenv("MB_ADAMW_RIDE")) e->adam_ride = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD")) e->ride_opts.dgrad = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD_BLOCKS")) e->ride_opts.dgrad_blocks = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGRAD_PARAMS")) e->ride_opts.dgrad_params = atol(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_DGELU_PARAMS")) e->ride_opts.dgelu_params = atol(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN")) e->ride_attn = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN_BLOCKS")) e->ride_attn_blocks = atoi(v);
-    if (const char* v = getenv("MB_ADAMW_RIDE_ATTN_PARAMS")) e->ride_attn_params = atol(v);
-    if (const char* v = getenv("MB_XL_SPLIT_R")) e->split_r = atoi(v) != 0;
-    if (const char* pv = getenv("MB_PREFETCH")) e->prefetch = atoi(pv);
     if (e->lo[0].k - e->lo[0].q != (size_t)cfg->d_model * cfg->d_model || e->lo[0].v - e->lo[0].k != e->lo[0].k - e->lo[0].q) e->fuse_qkv = false;
-    if (const char* v = getenv("MB_ADAMW_KEEP")) e->keep_enable = atoi(v);
     // lazy zeroing (engine_common.h): the seven GEMM weights of every layer, stored by the grouped launches of a pass that may overwrite
     e->ow_covers = (e->group_wgrad == 64 || e->group_wgrad == 128 || e->group_wgrad == 256) && cfg->d_inner % e->group_wgrad == 0 && cfg->d_model % e->group_wgrad == 0;
     e->stale_begin = e->lo[0].q; e->stale_end = e->wsum;
@@ -276,8 +247,6 @@ int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out) {
 }
 void mb_xlnet_destroy(mb_xlnet_engine* e) {
     if (!e) return;
-    if (e->side) hipStreamDestroy(e->side);
-    for (auto& ev : e->evs) if (ev) hipEventDestroy(ev);
     e->destroy_prof();
     e->drop_graphs();
     delete e;
@@ -508,7 +477,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                 wg[7].overwrite = 1;
             }
             if (!grouped) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
-            const bool riding = grouped && !e->deferred && e->ride_m != nullptr;
+            const bool riding = grouped && e->ride_m != nullptr;
             auto take_l = [&](size_t budget, int blocks) { return take_ride(l, budget, blocks); };
             CK(dgrad_with_riders(dt, EPI_DGELU, T, I, H, dzdA, H, e->W(o.w2), I, du, I, ws + w.u, I, G + o.b1, e->key(XS_LAYER0 + 8 * l + 2, pd), acc, st,
                                  riding, e->ride_opts, e->cu_count(), take_l));
@@ -542,9 +511,9 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                                  e->ride_opts, e->cu_count(), take_l));
             // (riders of the two relative-attention backward launches: 576 workgroups in 768 slots each at L = 50, latency-bound hosts)
             AdamRide rq = {}, rkv = {};
-            if (riding && e->ride_attn && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
+            if (riding && e->ride_opts.attn && L <= 128) {      // (the tiled kernels of L > 128 take no riders, whatever _BLOCKS says)
                 int free_slots = xlnet_attention_backward_free_slots(dt, L, B * nh, e->cu_count());
-                if (e->ride_attn_blocks > 0 && free_slots > 0) free_slots = e->ride_attn_blocks;
+                if (e->ride_opts.attn_blocks > 0 && free_slots > 0) free_slots = e->ride_opts.attn_blocks;
                 const int blocks = std::min(free_slots, 2 * e->cu_count()) / 8 * 8;
                 if (blocks >= 8) {
                     // same box, B = 48 L = 50: 4.253 ms without riders | 4.212 dgrad hosts only | 4.155 at 1.25 M + 0.83 M in the two attention launches |
@@ -552,7 +521,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                     // (later in the round, with the 128 x 64 tile's smaller dgrad riders: 4.040 ms at 1.8 M | 4.021 at 2.4 M | 4.011 at 3 M -- this:
                     //  1,250 per token; profiles/r06_final_defaults.txt; and further: 4.000 at 3 M | 3.983 at 4.2 M | 3.965 at 5.4 M, where the two
                     //  hosts take everything that is final -- this: 2,250 per token; profiles/r06_xlnet_ride_budget2.txt)
-                    const size_t budget = e->ride_attn_params > 0 ? (size_t)e->ride_attn_params : (size_t)2250 * (size_t)T;
+                    const size_t budget = e->ride_opts.attn_params > 0 ? (size_t)e->ride_opts.attn_params : (size_t)2250 * (size_t)T;
                     rq = take_ride(l, budget / 1024 * 1024, blocks);
                     rkv = take_ride(l, (budget * 2 / 3) / 1024 * 1024, blocks);
                 }
@@ -562,18 +531,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                                         G + o.rsb, G + o.seg, B, L, nh, e->key(XS_LAYER0 + 8 * l + 0, pd), st,
                                         e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, rq.blocks ? &rq : nullptr,
                                         rkv.blocks ? &rkv : nullptr, ws + w.vec, e->attn_stats(w), e->attn_pdsave(), e->perm));
-            if (grouped && e->deferred) {
-                if (!e->side) {
-                    CK((int)hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-                    e->evs.assign((size_t)2 * NL, nullptr);
-                    for (auto& ev : e->evs) CK((int)hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                }
-                CK((int)hipEventRecord(e->evs[2 * l], st));                       // every dY of the layer is final on `st`
-                CK((int)hipStreamWaitEvent(e->side, e->evs[2 * l], 0));
-                CK(gemm_grouped_tn_launch(dt, wg, nwg, wtile, e->side));
-                if (nwg == 8) CK(add_f32(G + o.r, (const float*)(ws + e->ws_rhalf), (size_t)H * H, e->side));
-                CK((int)hipEventRecord(e->evs[2 * l + 1], e->side));              // "weight gradients of layer l are final"
-            } else if (grouped) {
+            if (grouped) {
                 CK(e->prof_mark(2 * l, st));
                 CK(gemm_grouped_tn_launch(dt, wg, nwg, wtile, st));
                 CK(e->prof_mark(2 * l + 1, st));
@@ -624,10 +582,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                     CK(step_prologue(cp, st));
                 }
             }
-            // deferred join: main waits for layer l+1's launch only now (its dY buffers have the parity of layer l-1, written next)
-            if (grouped && e->deferred && l + 1 < NL) CK((int)hipStreamWaitEvent(st, e->evs[2 * (l + 1) + 1], 0));
         } else {
-            if (e->deferred && e->side) CK((int)hipStreamWaitEvent(st, e->evs[1], 0));       // weight gradients of layer 0
             CK(gather_drop_backward(dt, ws + e->ws_dxa, e->ids, e->ids ? G + e->word : (float*)(ws + e->ws_demb), T, H, e->key(XS_EMB, pd), st, acc));
             // deterministic mode: the integer sums become part of the fp32 gradients before anybody (AdamW, an exchange) reads them
             CK(grad_fold(acc, G, e->det_begin, e->det_end, st));
@@ -647,7 +602,7 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
                         loss_run, st));
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside launches of the backward of layers 0 .. NL-2 (mb_xlnet_backward: take_ride);
     // whether a launch really carried one is decided there, so the sweep below asks the engine what is still to do
-    const bool ride = e->adam_ride && m && v && e->c.dtype == DT_BF16 && e->group_wgrad > 0 && !e->deferred && e->c.n_layer > 1 && e->lo[0].q == 0 &&
+    const bool ride = e->ride_opts.ride && m && v && e->c.dtype == DT_BF16 && e->group_wgrad > 0 && e->c.n_layer > 1 && e->lo[0].q == 0 &&
                       !e->prof && !e->mems;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wsum;
@@ -687,7 +642,6 @@ int mb_xlnet_train_step(mb_xlnet_engine* e, const int64_t* input_ids, const floa
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if ((m == nullptr) != (v == nullptr) || (mode != 1 && mode != 2)) return MB_ERR_ARG;
-    if (e->deferred) return MB_ERR_MODE;          // MB_OVERLAP_WGRAD=1: the side-stream scheme is driven stage by stage (mb_xlnet_backward)
     if (e->head_mask || e->emb_in || e->perm || e->mems) return MB_ERR_MODE;      // head_mask / inputs_embeds / perm_mask / mems are arguments of explicit forwards only
     e->training = 1;
     CK(xl_prepare_pass(e, B * L, st));
@@ -782,7 +736,7 @@ int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const f
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if (!m || !v || (mode != 1 && mode != 2)) return MB_ERR_ARG;
-    if (e->deferred || e->head_mask || e->emb_in || e->perm || e->mems) return MB_ERR_MODE;
+    if (e->head_mask || e->emb_in || e->perm || e->mems) return MB_ERR_MODE;
     const int NL = c.n_layer;
     const std::vector<int> plan = dp_chunk_plan(NL);
     const int nb = (int)plan.size();
@@ -842,7 +796,7 @@ int mb_xlnet_set_profiling(mb_xlnet_engine* e, int on) {
     return e->set_profiling(on, e->c.n_layer);
 }
 int mb_xlnet_profile_wgrad_us(mb_xlnet_engine* e, float* avg_us) {
-    if (!e || !e->ow_covers || e->deferred) return MB_ERR_ARG;
+    if (!e || !e->ow_covers) return MB_ERR_ARG;
     return e->prof_span_us(0, e->c.n_layer, avg_us);
 }
 int mb_xlnet_profile_adamw_us(mb_xlnet_engine* e, float* us) {
@@ -1067,11 +1021,8 @@ int mb_xlnet_stage_grad_ranges(const mb_xlnet_engine* e, int stage, size_t* offs
     if (stage == 0) span(e->wsum, e->sh_end);
     else if (stage <= NL) {
         const int l = NL - stage;
-        auto wspan = [&](int k) { span(e->lo[k].q, k + 1 < NL ? e->lo[k + 1].q : e->wsum); };
-        if (!e->deferred) wspan(l);
-        else if (l + 1 < NL) wspan(l + 1);           // deferred join: a layer's weights are final one stage later
+        span(e->lo[l].q, l + 1 < NL ? e->lo[l + 1].q : e->wsum);      // the layer's GEMM weights
     } else if (stage == NL + 1) {
-        if (e->deferred) span(e->lo[0].q, NL > 1 ? e->lo[1].q : e->wsum);
         span(e->small_decay_begin, e->n_decay);      // seg_embed / layer_norm weights, word embedding, MAG weights, logits_proj.weight
         span(e->n_decay, e->n_trainable);            // every no-decay parameter
     } else return -1;

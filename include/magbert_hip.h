@@ -431,7 +431,7 @@ int mb_xlnet_grads_stale(const mb_xlnet_engine* e);
 /* the MAG-XLNet counterparts of mb_bert_train_step / mb_bert_load_batch / mb_bert_graph_stats (same contracts; one iteration of
  * train_epoch, multimodal_driver.py:359-386, for the xlnet-base-cased model).  The two parameter groups are [0, decay_count) and
  * [decay_count, trainable_count); the frozen transformer.mask_emb slot behind them is never updated (HF AdamW skips grad-less
- * parameters).  MB_ERR_MODE when the engine was created with MB_OVERLAP_WGRAD=1 (side-stream weight gradients). */
+ * parameters). */
 int mb_xlnet_train_step(mb_xlnet_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                         const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
                         uint64_t seed, uint64_t step, float* logits, float* loss, float* loss_run, float* m, float* v, float lr,
