@@ -183,6 +183,9 @@ class _Core(object):
         self.kind = kind                     # "bert" (mb_bert_*) or "xlnet" (mb_xlnet_*)
         if kind == "bert":
             check_bert_sizes(config)         # a clear message instead of the engine's "unsupported shape"
+        else:
+            from .xlnet import check_xlnet_sizes
+            check_xlnet_sizes(config, injection_index)
         self.injection_index = injection_index
         # the longest sequence this instance runs (both models) -- None or <= 128 keeps the limit of 128, above it the engine's attention
         # runs the tiled kernels (up to the position table; MAG-XLNet, which has no table: up to the kernels' 512)
@@ -977,7 +980,7 @@ class _MagBertBase(nn.Module):
 
     @classmethod
     def _config_beside(cls, path, num_labels):
-        # (MAG-BERT only: the MAG-XLNet classes share this from_pretrained and keep their default configuration)
+        # (MAG-BERT's; the MAG-XLNet classes share this from_pretrained and override this hook: xlnet._XlBase)
         return read_config_beside(path, num_labels) if cls.base_model_prefix == "bert" else None
 
 

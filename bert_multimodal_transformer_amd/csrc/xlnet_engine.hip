@@ -2,8 +2,8 @@
 // /root/reference/modeling.py:25-51), BASELINE.json config 4.  Same contract as engine.hip: one C call enqueues a whole pass,
 // caller-owned flat parameter / gradient / bf16-shadow / workspace buffers, reference state-dict names.
 //
-// Only the configuration the reference driver exercises is built (xlnet-base-cased: attn_type "bi", no mems / perm_mask /
-// target_mapping; multimodal_driver.py:363-370).  Sequence length: up to 128 the LDS-resident relative-attention kernels (MOSI: 50),
+// Built for the configuration the reference driver exercises (attn_type "bi"; multimodal_driver.py:363-370) at the widths d_model = 256 |
+// 512 | 768 (xlnet-base-cased) | 1024 (xlnet-large-cased: 24 layers, 16 heads, d_inner 4096) with heads of 64.  Sequence length: up to 128 the LDS-resident relative-attention kernels (MOSI: 50),
 // above it, up to 512, the tiled ones (xlnet_attention_tiled.hip) -- the dispatch is xlnet_attention_forward / _backward's, by L alone.
 //
 // Flat layout:  [ decay | no-decay | frozen ]
@@ -162,8 +162,8 @@ static void xl_build_layout(mb_xlnet_engine* e) {
         if (!tiled) { x.psave = w.take(PP * es); x.stats = 0; }
         else {
             // (passes of L <= 128 on such an engine still run the LDS-resident kernels, bit for bit: they keep a 128-row psave --
-            //  max_batch * 12 heads * 128 * 128 elements per layer, 393 KB per sample and layer in bf16: 604 MB at max_batch = 128,
-            //  12 layers, which the long passes never touch)
+            //  max_batch * n_head * 128 * 128 elements per layer -- xlnet-base: 393 KB per sample and layer in bf16, 604 MB at max_batch =
+            //  128, 12 layers; xlnet-large: 524 KB, 1.6 GB at 24 layers -- which the long passes never touch)
             x.psave = w.take((size_t)c.max_batch * nh * 128 * 128 * es);
             x.stats = w.take(xlnet_tiled_stats_floats(c.max_batch, c.max_seq, (int)nh) * 4);
         }
@@ -224,7 +224,9 @@ extern "C" {
 
 int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out) {
     if (!cfg || !out) return MB_ERR_ARG;
-    if (cfg->d_model != 768 || cfg->n_head * 64 != cfg->d_model) return MB_ERR_SHAPE;
+    // d_model 256 | 512 | 768 | 1024 (what the row kernels, MAG and the head are instantiated for), heads of 64, any depth >= 1
+    const int Hc = cfg->d_model;
+    if ((Hc != 256 && Hc != 512 && Hc != 768 && Hc != 1024) || cfg->n_head * 64 != Hc || cfg->n_layer < 1) return MB_ERR_SHAPE;
     if (cfg->d_inner % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1 || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->injection_index < 0 || cfg->injection_index >= cfg->n_layer) return MB_ERR_ARG;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
@@ -761,9 +763,10 @@ int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const f
     CK(dp_step_begin(comm, st, nf > 0));          // (sharded update: the previous step's all-gathers -- cut mode: awaited piece by piece)
     e->training = 1;
     CK(xl_prepare_pass(e, B * L, st));
-    int variant = 1;
-    for (int x : plan) variant = variant * 13 + x;
-    variant = (variant * 4 + comm->event_mode) * 2 + (comm->shard ? 1 : 0);
+    unsigned vh = 1;                                   // (unsigned: deep models have many pieces, the hash may wrap -- as engine.hip)
+    for (int x : plan) vh = vh * 13u + (unsigned)x;
+    vh = (vh * 4u + (unsigned)comm->event_mode) * 2u + (comm->shard ? 1u : 0u);
+    const int variant = (int)(vh & 0x7fffffffu) | 1;   // never 0, the single-process step's
     return train_step_impl(e, e->ws, c.visual_dim, c.acoustic_dim, c.num_labels, input_ids, visual, acoustic, attention_mask, token_type_ids,
                            labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2, eps, weight_decay, opt_step,
                            correct_bias, grad_scale, loss_scale, mode, e->prof, st,

@@ -77,6 +77,15 @@ def bert_config(model, num_labels=1):
     return BertConfig.large(num_labels=num_labels) if model == "bert-large-uncased" else BertConfig(num_labels=num_labels)
 
 
+XLNET_MODELS = ("xlnet-base-cased", "xlnet-large-cased")      # everything that takes prepare_xlnet_input and the MAG-XLNet classes
+
+
+def xlnet_config(model, num_labels=1):
+    """the XLNetConfig a --model name stands for"""
+    from .xlnet import XLNetConfig
+    return XLNetConfig.large(num_labels=num_labels) if model == "xlnet-large-cased" else XLNetConfig(num_labels=num_labels)
+
+
 def get_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--dataset", type=str, choices=["mosi", "mosei"], default="mosi")
@@ -87,7 +96,7 @@ def get_parser():
     parser.add_argument("--n_epochs", type=int, default=40)
     parser.add_argument("--beta_shift", type=float, default=1.0)
     parser.add_argument("--dropout_prob", type=float, default=0.5)
-    parser.add_argument("--model", type=str, choices=["bert-base-uncased", "bert-large-uncased", "xlnet-base-cased"],
+    parser.add_argument("--model", type=str, choices=["bert-base-uncased", "bert-large-uncased", "xlnet-base-cased", "xlnet-large-cased"],
                         default="bert-base-uncased")
     parser.add_argument("--learning_rate", type=float, default=1e-5)
     parser.add_argument("--gradient_accumulation_step", type=int, default=1)
@@ -152,7 +161,7 @@ def convert_to_features(examples, max_seq_length, tokenizer):
     row of the word it belongs to (a gather by owner index), the sequence is cut to max_seq_length - 2 pieces, and the
     model-specific layout (special tokens, padding side, segment ids) is applied by prepare_bert_input / prepare_xlnet_input."""
     layout = {"bert-base-uncased": prepare_bert_input, "bert-large-uncased": prepare_bert_input,
-              "xlnet-base-cased": prepare_xlnet_input}[args.model]
+              "xlnet-base-cased": prepare_xlnet_input, "xlnet-large-cased": prepare_xlnet_input}[args.model]
     room = max_seq_length - 2
     out = []
     for (words, visual, acoustic), label_id, _segment in examples:
@@ -206,9 +215,9 @@ def get_tokenizer(model):
         raise RuntimeError("transformers tokenizers unavailable: %s" % e)
     if model in BERT_MODELS:
         return BertTokenizer.from_pretrained(model)
-    elif model == "xlnet-base-cased":
+    elif model in XLNET_MODELS:
         return XLNetTokenizer.from_pretrained(model)
-    raise ValueError("Expected 'bert-base-uncased', 'bert-large-uncased' or 'xlnet-base-cased, but received {}".format(model))
+    raise ValueError("Expected 'bert-base-uncased', 'bert-large-uncased', 'xlnet-base-cased' or 'xlnet-large-cased', but received {}".format(model))
 
 
 def features_to_dataset(features):
@@ -324,7 +333,7 @@ def set_up_data_loader():
     rank, world = _dist()
     if args.synthetic:
         n = args.synthetic
-        lay = "xlnet" if args.model == "xlnet-base-cased" else "bert"
+        lay = "xlnet" if args.model in XLNET_MODELS else "bert"
         train_dataset = synthetic_dataset(n, args.max_seq_length, V, A, 1234, layout=lay)
         dev_dataset = synthetic_dataset(max(8, n // 6), args.max_seq_length, V, A, 1235, layout=lay)
         test_dataset = synthetic_dataset(max(8, n // 2), args.max_seq_length, V, A, 1236, layout=lay)
@@ -386,14 +395,16 @@ def prep_for_training(num_train_optimization_steps: int):
         else:       # offline: fresh init by the reference's init law
             model = MAG_BertForSequenceClassification(bert_config(args.model), multimodal_config, visual_dim=V,
                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
-    elif args.model == "xlnet-base-cased":
-        from .xlnet import MAG_XLNetForSequenceClassification, XLNetConfig
+    elif args.model in XLNET_MODELS:
+        from .xlnet import MAG_XLNetForSequenceClassification, read_xlnet_config_beside
         if args.pretrained:
+            # (the checkpoint directory's config.json names the model size; without one: this --model's configuration)
             model = MAG_XLNetForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt, max_seq_length=args.max_seq_length)
+                compute_dtype=dt, max_seq_length=args.max_seq_length,
+                config=read_xlnet_config_beside(args.pretrained, 1) or xlnet_config(args.model))
         else:
-            model = MAG_XLNetForSequenceClassification(XLNetConfig(num_labels=1), multimodal_config, visual_dim=V,
+            model = MAG_XLNetForSequenceClassification(xlnet_config(args.model), multimodal_config, visual_dim=V,
                                                        acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     model.to(_device())
     optimizer = AdamW(optimizer_grouped_parameters(model), lr=args.learning_rate)

@@ -22,8 +22,56 @@ from .bert import _BaseFn, _Core, _EngineFn, _FusedStep, _MagBertBase, _attach_p
 from .global_configs import ACOUSTIC_DIM, VISUAL_DIM, XLNET_INJECTION_INDEX
 
 
+SUPPORTED_D_MODELS = (256, 512, 768, 1024)      # what the row kernels, MAG and the head are instantiated for (heads of 64)
+
+
+def check_xlnet_sizes(config, injection_index=None):
+    """The model sizes the MAG-XLNet engine runs: d_model in SUPPORTED_D_MODELS with heads of 64 (256 / 4, 512 / 8, xlnet-base 768 / 12,
+    xlnet-large 1024 / 16), any depth, d_inner a multiple of 128; the MAG injection in front of an existing layer.  Raises ValueError
+    otherwise (modelled on bert.check_bert_sizes)."""
+    H, nh, I, NL = int(config.d_model), int(config.n_head), int(config.d_inner), int(config.n_layer)
+    sizes = ", ".join(map(str, SUPPORTED_D_MODELS))
+    if H not in SUPPORTED_D_MODELS:
+        raise ValueError("d_model = %d: the HIP engine runs d_model %s (heads of 64)" % (H, sizes))
+    if nh * 64 != H:
+        raise ValueError("n_head = %d with d_model = %d: the relative-attention kernels take heads of 64 (%d heads); d_model %s"
+                         % (nh, H, H // 64, sizes))
+    if I % 128 or I < 128:
+        raise ValueError("d_inner = %d: must be a multiple of 128 (d_model %s)" % (I, sizes))
+    if NL < 1:
+        raise ValueError("n_layer = %d: at least one layer (d_model %s)" % (NL, sizes))
+    if injection_index is not None and not 0 <= int(injection_index) < NL:
+        raise ValueError("injection_index = %d: MAG is injected in front of a layer, 0 <= injection_index < n_layer = %d"
+                         % (int(injection_index), NL))
+
+
 class XLNetConfig(object):
-    """The subset of transformers.XLNetConfig (xlnet-base-cased) the path reads."""
+    """The subset of transformers.XLNetConfig the path reads (xlnet-base-cased defaults).
+
+    Sizes the engine runs (check_xlnet_sizes, applied when a model is constructed): d_model 256, 512, 768 or 1024 with
+    n_head = d_model / 64, any n_layer >= 1, d_inner a multiple of 128 -- e.g. xlnet-large-cased is XLNetConfig.large():
+    d_model=1024, n_head=16, n_layer=24, d_inner=4096."""
+
+    KEYS = ("vocab_size", "d_model", "n_layer", "n_head", "d_inner", "ff_activation", "attn_type", "initializer_range", "layer_norm_eps",
+            "dropout", "mem_len", "reuse_len", "bi_data", "clamp_len", "same_length", "summary_type", "summary_use_proj",
+            "summary_activation", "summary_last_dropout")
+
+    @classmethod
+    def large(cls, **kwargs):
+        """xlnet-large-cased: 24 layers x 1024 wide, 16 heads, d_inner 4096 (361 M parameters)"""
+        kw = dict(d_model=1024, n_layer=24, n_head=16, d_inner=4096)
+        kw.update(kwargs)
+        return cls(**kw)
+
+    @classmethod
+    def from_json_file(cls, path, **kwargs):
+        """A HuggingFace `config.json`: only the keys this class knows (KEYS) are read, everything else in the file is ignored."""
+        import json
+        with open(path) as f:
+            d = json.load(f)
+        kw = {k: d[k] for k in cls.KEYS if k in d}
+        kw.update(kwargs)
+        return cls(**kw)
 
     def __init__(self, vocab_size=32000, d_model=768, n_layer=12, n_head=12, d_inner=3072, ff_activation="gelu",
                  attn_type="bi", initializer_range=0.02, layer_norm_eps=1e-12, dropout=0.1, mem_len=None, reuse_len=None,
@@ -31,7 +79,8 @@ class XLNetConfig(object):
                  summary_activation="tanh", summary_last_dropout=0.1, num_labels=1, **kwargs):
         if ff_activation != "gelu" or attn_type != "bi" or bi_data or clamp_len != -1 or reuse_len not in (None, 0) \
                 or summary_type != "last" or not summary_use_proj or summary_activation != "tanh":
-            raise NotImplementedError("only the xlnet-base-cased configuration used by multimodal_driver.py is built")
+            raise NotImplementedError("only the configuration of the published XLNet checkpoints that multimodal_driver.py uses is built "
+                                      "(gelu, attn_type bi, summary: last + tanh projection)")
         self.mem_len = mem_len          # > 0 with use_cache: forward() also returns new_mems (xlnet.py:81-91, 363-365, 406-407)
         self.vocab_size = vocab_size
         self.d_model = d_model
@@ -56,6 +105,26 @@ class _XlBase(_MagBertBase):
     @staticmethod
     def _default_config(num_labels):
         return XLNetConfig(num_labels=num_labels)
+
+    @classmethod
+    def _config_beside(cls, path, num_labels):
+        return read_xlnet_config_beside(path, num_labels)
+
+
+def read_xlnet_config_beside(path, num_labels=1):
+    """XLNetConfig from the `config.json` in the checkpoint directory `path` (or next to the checkpoint file `path`) if that file holds
+    XLNet's size keys (d_model, n_layer, n_head, d_inner); None if there is no such file or it describes another model family"""
+    import json
+    import os
+    d = path if os.path.isdir(path) else os.path.dirname(os.path.abspath(path))
+    j = os.path.join(d, "config.json")
+    if not os.path.isfile(j):
+        return None
+    with open(j) as f:
+        keys = json.load(f)
+    if not all(k in keys for k in ("d_model", "n_layer", "n_head", "d_inner")):
+        return None
+    return XLNetConfig.from_json_file(j, num_labels=num_labels)
 
 
 class MAG_XLNetModel(_XlBase):

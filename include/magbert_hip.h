@@ -9,8 +9,8 @@
  *
  * dtype: 0 = fp32 "parity mode" (exact-fp32 MFMA, logits within 1e-3 of the CPU reference),
  *        1 = bf16 "perf mode" (bf16 activations / MFMA operands, fp32 accumulate, fp32 master weights).
- * All row-major.  T = B*L tokens, H = the hidden size (256 | 512 | 768 | 1024 for the row operators, MAG and the MAG-BERT engine;
- * the MAG-XLNet engine: 768), heads of 64.  Reference citations are relative to /root/reference.
+ * All row-major.  T = B*L tokens, H = the hidden size (256 | 512 | 768 | 1024 for the row operators, MAG and both engines), heads
+ * of 64.  Reference citations are relative to /root/reference.
  */
 #ifndef MAGBERT_HIP_H
 #define MAGBERT_HIP_H
@@ -297,6 +297,8 @@ int mb_bert_profile_adamw_us(mb_bert_engine* e, float* us);
  * Same calling conventions as the mb_bert_* family.  Backward stages: 0 = summary + logits_proj, 1..n_layer = layers (last
  * first; the MAG backward runs inside the stage of layer `injection_index`), n_layer+1 = word embedding. */
 typedef struct {
+    /* d_model: 256 | 512 | 768 (xlnet-base-cased) | 1024 (xlnet-large-cased) with n_head * 64 == d_model; n_layer >= 1;
+     * d_inner % 128 == 0; 0 <= injection_index < n_layer (else MB_ERR_ARG).  Any other size: mb_xlnet_create returns MB_ERR_SHAPE. */
     int vocab_size, d_model, n_layer, n_head, d_inner, num_labels;
     int visual_dim, acoustic_dim, injection_index;
     float layer_norm_eps, mag_layer_norm_eps, beta_shift;

@@ -5,8 +5,8 @@
 // plain C++ process, so a GPU-box visit costs seconds instead of a Python/torch start-up, and rocprofv3 can wrap it.
 //
 //   step_bench [--model bert|xlnet] [--steps K] [--warmup W] [--batch B] [--seq L] [--dtype bf16|fp32] [--visual V] [--layers N]
-//              [--hidden H] [--heads n] [--inter I]       (MAG-BERT only; bert-large-uncased = --layers 24 --hidden 1024 --heads 16 --inter 4096;
-//                                                          --heads defaults to H / 64, --inter to 4 H)
+//              [--hidden H] [--heads n] [--inter I]       (both models; bert-large-uncased / xlnet-large-cased = --layers 24 --hidden 1024
+//                                                          --heads 16 --inter 4096; --heads defaults to H / 64, --inter to 4 H)
 //              [--graph 0|1|2] [--h2d 0|1|2] [--nbatch n] [--dp 0|1] [--wire fp32|bf16] [--sparse 0|1] [--timing 0|1] [--shard 0|1]
 //   --dp 1:  the data-parallel step, mb_bert_train_step_dp, with a ONE-rank RCCL communicator created here through the C ABI
 //            (mb_comm_unique_id / mb_comm_create_rccl): the N > 1 code path -- graph chain, comm stream, events, ncclAllReduce /
@@ -55,7 +55,6 @@ int main(int argc, char** argv) {
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
-    if (xl && hidden != 768) { fprintf(stderr, "--hidden/--heads/--inter: MAG-BERT only (the MAG-XLNet engine is built for 768)\n"); return 1; }
     mb_bert_config c = {};
     c.vocab_size = 30522; c.hidden_size = hidden; c.num_layers = layers; c.num_heads = heads; c.intermediate_size = inter;
     c.max_position = 512; c.type_vocab = 2; c.num_labels = 1; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
@@ -67,7 +66,7 @@ int main(int argc, char** argv) {
     if (xl) {
         if (!graph || dp) { fprintf(stderr, "--model xlnet: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
         mb_xlnet_config xc = {};
-        xc.vocab_size = 32000; xc.d_model = 768; xc.n_layer = layers; xc.n_head = 12; xc.d_inner = 3072; xc.num_labels = 1;
+        xc.vocab_size = 32000; xc.d_model = hidden; xc.n_layer = layers; xc.n_head = heads; xc.d_inner = inter; xc.num_labels = 1;
         xc.visual_dim = V; xc.acoustic_dim = A; xc.injection_index = 1;
         xc.layer_norm_eps = 1e-12f; xc.mag_layer_norm_eps = 1e-5f; xc.beta_shift = 1.0f;
         xc.dropout = 0.1f; xc.summary_last_dropout = 0.1f; xc.mag_dropout = 0.5f; xc.dtype = dtype; xc.max_batch = B; xc.max_seq = L;
@@ -185,7 +184,7 @@ int main(int argc, char** argv) {
     const double host_ms = std::chrono::duration<double, std::milli>(t1 - t0).count() / steps;
     const double wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count() / steps;
     char shape[64] = "";
-    if (!xl && (hidden != 768 || heads != 12 || inter != 3072)) snprintf(shape, sizeof shape, " hidden=%d heads=%d inter=%d", hidden, heads, inter);
+    if ((hidden != 768 || heads != 12 || inter != 3072)) snprintf(shape, sizeof shape, " hidden=%d heads=%d inter=%d", hidden, heads, inter);
     printf("step_bench %sdtype=%s B=%d L=%d V=%d layers=%d%s graph=%d h2d=%d : %.3f ms/step (events) %.3f ms/step (wall) host-enqueue %.3f ms/step "
            "%.1f samples/s last-loss %.4f mean-loss %.4f\n",
            xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, shape, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
