@@ -13,9 +13,9 @@ from .global_configs import ACOUSTIC_DIM, VISUAL_DIM, TEXT_DIM
 from .modeling import MAG
 from .bert import BertConfig, MAG_BertModel, MAG_BertForSequenceClassification
 from .xlnet import XLNetConfig, MAG_XLNetModel, MAG_XLNetForSequenceClassification
-from .optimization import AdamW, get_linear_schedule_with_warmup
+from .optimization import AdamW, get_linear_schedule_with_warmup, layerwise_lr_groups
 from .multimodal_driver import MultimodalConfig
 
 __all__ = ["MAG", "MAG_BertModel", "MAG_BertForSequenceClassification", "BertConfig", "XLNetConfig", "MAG_XLNetModel", "MAG_XLNetForSequenceClassification", "MultimodalConfig", "AdamW",
-           "get_linear_schedule_with_warmup", "ACOUSTIC_DIM", "VISUAL_DIM", "TEXT_DIM"]
+           "get_linear_schedule_with_warmup", "layerwise_lr_groups", "ACOUSTIC_DIM", "VISUAL_DIM", "TEXT_DIM"]
 __version__ = "0.1.0"

@@ -143,6 +143,12 @@ PROTOTYPES = {
     "mb_xlnet_load_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp), _vp]),
     "mb_xlnet_graph_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "mb_xlnet_trainable_count": (_sz, [_vp]),
+    "mb_bert_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mb_bert_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mb_bert_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
+    "mb_xlnet_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mb_xlnet_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mb_xlnet_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
     "mb_xlnet_stage_grad_ranges": (_i, [_vp, _i, C.POINTER(_sz), C.POINTER(_sz), _i]),
     # data parallel (csrc/comm.hip)
     "mb_comm_unique_id": (_i, [_vp]),

@@ -257,6 +257,7 @@ class _Core(object):
             self.ws = None
         self.handle = h
         self._optional = (None, None, None, None, None)    # a new engine starts without head_mask / inputs_embeds / position_ids / perm_mask
+        self._update_map = None                            # ... and without a segment map of update classes (train_step)
         self.max_B, self.max_L = B, L
 
     def _comm_join(self):
@@ -569,6 +570,8 @@ class _Core(object):
         if comm is not None and opt is None:
             raise ValueError("the data-parallel single-call step ends with the optimizer (micro-steps exchange nothing)")
         extra = () if comm is None else (comm.handle,)
+        if opt is not None:
+            self._install_update_classes(opt)
         if self.kind == "bert" and self.grads._version != getattr(self, "_gz_version", -1):
             # torch wrote into the flat gradient buffer since the engine last looked (torch_wrote_grads): the sweep of this update
             # cannot take the word rows outside its batches for zero (include/magbert_hip.h: mb_bert_distrust_word_stamps)
@@ -583,6 +586,33 @@ class _Core(object):
         self._gz = opt is not None          # the fused AdamW left the gradients zeroed / a micro-step left them populated
         self._gz_version = self.grads._version
         return logits
+
+    def _install_update_classes(self, opt):
+        """classed optimizers (AdamW.flat_step_args with a "map"): the segment map goes to the engine when it changes -- it is part of a
+        captured graph's identity -- and this step's per-class values every time (include/magbert_hip.h: mb_*_set_update_map /
+        _set_update_values).  The two-group optimizer clears a map another optimizer left behind; micro-steps leave it alone."""
+        seg = opt.get("map")
+        key = None if seg is None else (tuple(seg[0]), tuple(seg[1]))
+        if key != getattr(self, "_update_map", None):
+            if key is None:
+                _lib.check(self._fn("set_update_map")(self.handle, 0, 0, None, None))
+            else:
+                bounds = (C.c_size_t * len(key[0]))(*key[0])
+                classes = (C.c_int * len(key[1]))(*key[1])
+                _lib.check(self._fn("set_update_map")(self.handle, max(key[1]) + 1, len(key[1]), bounds, classes))
+            self._update_map = key
+        if key is not None:
+            cv = opt["classes"]
+            n = len(cv["lr"])
+            fl = lambda xs: (C.c_float * n)(*xs)
+            _lib.check(self._fn("set_update_values")(self.handle, n, fl(cv["lr"]), fl(cv["beta1"]), fl(cv["beta2"]), fl(cv["eps"]),
+                                                     fl(cv["weight_decay"]), (C.c_int * n)(*cv["correct_bias"])))
+
+    def update_stats(self):
+        """(elements updated by riders, elements updated by the end-of-step sweep, segments of the map) of the last single-call update"""
+        ridden, swept, segs = C.c_size_t(), C.c_size_t(), C.c_int()
+        _lib.check(self._fn("update_stats")(self.handle, C.byref(ridden), C.byref(swept), C.byref(segs)))
+        return ridden.value, swept.value, segs.value
 
     def stage_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, loss_scale=1.0, mode=1):
         """forward + MSE + backward of one training step cut at the backward stages (include/magbert_hip.h: mb_bert_stage_forward /
@@ -1061,7 +1091,7 @@ class _FusedStep(object):
         if why is None and optimizer is not None:
             opt = optimizer.flat_step_args(core) if hasattr(optimizer, "flat_step_args") else None
             if opt is None:
-                why = "the optimizer is not the two-group AdamW over this model's flat buffer"
+                why = "the optimizer's parameter groups do not map onto this model's flat buffer"
         if graph is True and why is not None:
             raise _lib.MagbertError("single-call step unavailable: " + why)
         if why is not None or graph is False:

@@ -215,4 +215,81 @@ int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const Adam
     return (int)hipGetLastError();
 }
 
+// The sweep of a classed step (kernels.h AdamPieces): adamw_sweep_kernel with its ranges read from a table of up to MB_SWEEP_PIECES_MAX
+// pieces whose running sums the host laid out, every piece with its class's slot of `cls`, and the class's weight_decay in place of
+// "i < n_decay".  A block walks the pieces in front of its own with scalar loads of the kernel arguments only.
+template <bool NT>
+__global__ void __launch_bounds__(256) adamw_sweep_classed_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                                  float* __restrict__ v, bf16* __restrict__ shadow, const AdamPieces R,
+                                                                  size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end,
+                                                                  const AdamArgs* __restrict__ cls, WordSkip ws) {
+    constexpr int UNR = 2;
+    const size_t total4 = R.start4[R.count];
+    const size_t per = ((total4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const size_t vb = (size_t)blockIdx.x * per, ve = min(total4, vb + per);
+    const bool skip_on = ws.stamp != nullptr && ws.state[1] != 0u;
+    const uint32_t stamp_no = skip_on ? ws.state[0] : 0u;
+    const size_t all = ~(size_t)0;
+#pragma unroll 1
+    for (int k = 0; k < R.count; ++k) {
+        const size_t off = R.start4[k], nxt = R.start4[k + 1];
+        if (nxt <= vb) continue;
+        if (off >= ve) break;
+        const size_t lo = max(vb, off), hi = min(ve, nxt);
+        if (lo >= hi) continue;
+        const AdamArgs a = cls[R.slot[k]];
+        const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+        const float decay = a.lr * a.weight_decay;
+        const size_t base4 = (size_t)R.begin4[k] - off;          // quad index in the buffers = base4 + index in the laid-out pieces
+        const size_t begin = base4 + lo + threadIdx.x, end = base4 + hi;
+        for (size_t i4 = begin; i4 < end; i4 += 256 * UNR) {
+            AdamQuad q[UNR];
+            bool live[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const size_t i = (i4 + (size_t)u * 256) * 4;
+                live[u] = true;
+                if (i4 + (size_t)u * 256 < end) {
+                    if (skip_on && i >= ws.begin && i < ws.end) live[u] = ws.stamp[(uint32_t)(i - ws.begin) / ws.row_len] == stamp_no;
+                    q[u] = adam_load<NT>(p, g, m, v, i, live[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u)
+                if (i4 + (size_t)u * 256 < end)
+                    adam_update_store<NT>(q[u], p, g, m, v, shadow, (i4 + (size_t)u * 256) * 4, a, omb1, omb2, decay, all, sh_begin, sh_end,
+                                          keep_begin, keep_end, live[u] ? 1 : 0);
+        }
+    }
+}
+
+int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
+                        size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st) {
+    if (r.count < 0 || r.count > MB_SWEEP_PIECES_MAX || !cls) return MB_ERR_ARG;
+    if (r.count && r.start4[0] != 0u) return MB_ERR_ARG;
+    for (int k = 0; k < r.count; ++k)
+        if (r.start4[k + 1] < r.start4[k] || r.slot[k] >= MB_CLASSES_MAX) return MB_ERR_SHAPE;
+    const size_t n4 = r.count ? r.start4[r.count] : 0;
+    if (n4 == 0) return MB_OK;
+    if ((sh_begin % 4) || (sh_end % 4) || (keep_begin % 4) || (keep_end % 4)) return MB_ERR_SHAPE;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MB_ERR_SHAPE;
+    if (skip.stamp && (!skip.state || skip.row_len == 0 || (skip.begin | skip.end | skip.row_len) % 4 || skip.end < skip.begin ||
+                       skip.end - skip.begin > 0xffffffffull)) return MB_ERR_SHAPE;
+    {   // (as adamw_sweep: one launch, one line)
+        static int log = -1;
+        if (log < 0) { const char* e = getenv("MB_GEMM_LOG"); log = e ? atoi(e) : 0; }
+        if (log) fprintf(stderr, "[magbert adamw] n=%zu\n", n4 * 4);
+    }
+    unsigned grid = (unsigned)((n4 + 255) / 256);
+    if (grid > 256 * 16) grid = 256 * 16;
+    static int nt = -1, vgrid = 0;
+    if (nt < 0) { const char* e = getenv("MB_ADAMW_NT"); nt = e ? atoi(e) : 1; const char* g2 = getenv("MB_ADAMW_GRID"); vgrid = g2 ? atoi(g2) : 0; }
+    if (vgrid > 0 && (unsigned)vgrid < grid) grid = (unsigned)vgrid;
+    if (nt) hipLaunchKernelGGL(adamw_sweep_classed_kernel<true>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
+                               keep_begin, keep_end, cls, skip);
+    else hipLaunchKernelGGL(adamw_sweep_classed_kernel<false>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
+                            keep_begin, keep_end, cls, skip);
+    return (int)hipGetLastError();
+}
+
 }  // namespace mb

@@ -421,6 +421,7 @@ void mb_bert_destroy(mb_bert_engine* e) {
     for (auto& ev : e->opt_ev) if (ev) hipEventDestroy(ev);
     e->destroy_prof();
     e->drop_graphs();
+    e->free_class_table();
     delete e;
 }
 int mb_bert_num_tensors(const mb_bert_engine* e) { return (int)e->tensors.size(); }
@@ -557,13 +558,21 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
     auto take_ride = [&](int l, size_t budget, int blocks) -> AdamRide {
         AdamRide r = {};
         if (!e->ride_m || !e->ride_v || l + 1 >= e->c.num_layers || blocks < 8 || e->ride_cursor <= e->lo[l + 1].wqkv) return r;
-        size_t take = std::min(e->ride_cursor - e->lo[l + 1].wqkv, budget) / 1024 * 1024;
+        // classed step (StepMixin::n_classes): the slice stays inside the segment that holds its top element and reads that class's slot
+        size_t floor = e->lo[l + 1].wqkv;
+        const AdamArgs* dyn = e->adam_state(e->ws);
+        if (e->n_classes > 0) {
+            size_t sb = 0; int cl = 0;
+            e->ride_segment(e->ride_cursor, &sb, &cl);
+            floor = std::max(floor, sb); dyn = e->class_state(e->ws) + cl;
+        }
+        size_t take = std::min(e->ride_cursor - floor, budget) / 1024 * 1024;
         const size_t re = e->ride_cursor, rb = re - take;
         const bool sh_ok = e->c.dtype != DT_BF16 || (e->sh_begin <= rb && re <= e->sh_end);
         if (take == 0 || rb % 4 || !sh_ok) return r;
         const bool keep = e->keep_in_step() && e->stale_begin <= rb && re <= e->stale_end;
         r = AdamRide{e->P + rb, e->G + rb, e->ride_m + rb, e->ride_v + rb, e->c.dtype == DT_BF16 ? (bf16*)(e->SH + rb * 2) : nullptr,
-                     take / 4, e->adam_state(e->ws), blocks / 8 * 8, keep ? 0 : 1};
+                     take / 4, dyn, blocks / 8 * 8, keep ? 0 : 1};
         e->ride_cursor = rb;
         return r;
     };
@@ -821,7 +830,7 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
     // (experiment) the layers' weights are updated by their own weight-gradient launches: single segment, known-zero gradients,
     // in-line 128 x 128 grouped launches, the layers' GEMM weights at the head of the decay slab
     const bool fuse = e->adam_in_wgrad && m && v && nseg == 1 && e->ow_pass && e->grouped && e->group_wgrad == 128 && NL > 0 &&
-                      e->lo[0].wqkv == 0 && !e->prof;
+                      e->lo[0].wqkv == 0 && !e->prof && e->n_classes == 0;      // (one set of scalars: off in a classed step)
     e->fuse_m = fuse ? m : nullptr; e->fuse_v = fuse ? v : nullptr;
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside the weight-gradient launches of layers 0 .. NL-2; whether a launch
     // really carried one is decided there, so the sweep below asks the engine which layers are still to do
@@ -837,6 +846,24 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_params;
         CK(e->prof_mark(2 * NL, st));
+        e->upd_ridden = ride ? e->wp - e->ride_cursor : 0; e->upd_swept = n - (fuse ? e->wp : e->upd_ridden);
+        e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
+        if (e->n_classes > 0) {
+            // Classed step (kernels.h AdamPieces): the same ranges cut at the segment boundaries, every piece with its class's slot, ONE
+            // launch; the word rows and the keep range as below
+            if (nseg != 1) return MB_ERR_MODE;
+            AdamPieces pieces;
+            CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wp, e->wp, n));
+            const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
+            const bool keep = e->keep_in_step();
+            WordSkip ws_ = {};
+            if (skip) ws_ = WordSkip{e->stamp_table(ws), e->stamp_state(ws), e->word, e->word + (size_t)e->c.vocab_size * e->c.hidden_size,
+                                      (uint32_t)e->c.hidden_size};
+            CK(adamw_sweep_classed(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, pieces, e->sh_begin, e->sh_end,
+                                   keep ? e->stale_begin : 0, keep ? e->stale_end : 0, e->class_state(ws), ws_, st));
+            CK(e->prof_mark(2 * NL + 1, st));
+            return MB_OK;
+        }
         // The sweep proper: what the riders left of the layers, the rest of the decay slab, the no-decay slab.  ONE launch over that list
         // (kernels.h AdamRanges; MB_ADAMW_ONE_SWEEP=0: one launch per range), which leaves the gradients of the word rows this update's
         // batches did not touch alone when the engine can vouch for their zeros (WordSkip, StepMixin::stamp_live: the prologue put the
@@ -889,6 +916,20 @@ static int between_segments(mb_bert_engine* e, int seg, int nseg, float* m, floa
     return MB_OK;
 }
 
+int mb_bert_set_update_map(mb_bert_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_map(e->tensors, e->n_params, n_classes, n_segments, boundaries, classes);
+}
+int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                              const float* weight_decay, const int* correct_bias) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_values(n_classes, lr, beta1, beta2, eps, weight_decay, correct_bias);
+}
+int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments) {
+    if (!e) return MB_ERR_ARG;
+    return e->update_stats(ridden, swept, segments);
+}
+
 int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                        const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
                        uint64_t seed, uint64_t step, float* logits, float* loss, float* loss_run, float* m, float* v, float lr,
@@ -905,7 +946,7 @@ int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float*
     e->training = 1;
     CK(prepare_pass(e, T, st));
     int nseg = 1;
-    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof) {
+    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof && e->n_classes == 0) {
         nseg = c.num_layers / e->opt_chunk + 1;
         if (!e->opt_side) {
             CK((int)hipStreamCreateWithFlags(&e->opt_side, hipStreamNonBlocking));
@@ -1005,6 +1046,7 @@ int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const flo
                           float beta1, float beta2, float eps, float weight_decay, int opt_step, int correct_bias, float grad_scale,
                           float loss_scale, int mode, void* stream, mb_comm* comm) {
     hipStream_t st = (hipStream_t)stream;
+    if (e && e->n_classes > 0) return MB_ERR_MODE;          // update classes: the single-process step only
     if (!e || !e->P || !e->G || !e->ws || !comm) return MB_ERR_ARG;
     const mb_bert_config& c = e->c;
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;

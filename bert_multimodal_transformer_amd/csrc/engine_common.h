@@ -11,6 +11,7 @@
 #include "../../include/magbert_hip.h"
 
 using namespace mb;
+static_assert(MB_UPDATE_CLASSES_MAX == MB_CLASSES_MAX && MB_UPDATE_SEGMENTS_MAX == MB_SEGMENTS_MAX, "public limits = the kernels' limits");
 
 namespace {
 
@@ -216,6 +217,7 @@ struct StepGraph {
     int variant;                                    // which segmentation (0 = the single-process step, else a hash of the data-parallel plan)
     const void* tag;                                // whose events the graphs' nodes record (the mb_comm of a data-parallel step), else null
     std::vector<hipGraph_t> graph; std::vector<hipGraphExec_t> exec;
+    size_t ridden = 0, swept = 0; int segments = 0; // what the captured update covers (StepMixin::upd_*: a replay enqueues nothing on the host)
     void destroy() {
         for (auto x : exec) if (x) hipGraphExecDestroy(x);
         for (auto g : graph) if (g) hipGraphDestroy(g);
@@ -413,6 +415,83 @@ struct StepMixin {
         return MB_OK;
     }
     AdamArgs* adam_state(char* ws) const { return (AdamArgs*)(ws + ws_state); }
+    // Update classes (kernels.h AdamPieces, include/magbert_hip.h mb_*_set_update_map).  n_classes == 0 -- the default -- is the step of the
+    // two parameter groups: nothing below is looked at.  Otherwise the layout's update range [0, seg_bounds.back()) is cut into segments,
+    // segment s = [seg_bounds[s], seg_bounds[s + 1]) belongs to class seg_class[s], and the step prologue writes the scalars of every class
+    // (class_vals: what mb_*_set_update_values handed over) into a table of their own: device memory the engine allocates before the
+    // first classed update and keeps until it is destroyed -- the workspace, whose size callers have planned with, stays as it was, and
+    // so do the two slots of adam_state and the dropout keys behind them.  map_version joins the identity of a captured
+    // graph: rider slices and sweep pieces are cut at the segment boundaries at capture time; the values never re-capture.
+    struct ClassVals { float lr, beta1, beta2, eps, weight_decay; int correct_bias; };
+    int n_classes = 0, map_version = 0;
+    std::vector<size_t> seg_bounds;
+    std::vector<int> seg_class;
+    std::vector<ClassVals> class_vals;
+    AdamArgs* class_table = nullptr;
+    size_t upd_ridden = 0, upd_swept = 0; int upd_segments = 0;       // the last enqueued update (mb_*_update_stats)
+    int ensure_class_table() {          // (never inside a capture: train_step_impl calls it before the prologue)
+        if (!class_table) CK((int)hipMalloc((void**)&class_table, (size_t)MB_CLASSES_MAX * sizeof(AdamArgs)));
+        return MB_OK;
+    }
+    void free_class_table() { if (class_table) { hipFree(class_table); class_table = nullptr; } }
+    AdamArgs* class_state(char*) const { return class_table; }
+    int set_update_map(const std::vector<TensorInfo>& tensors, size_t n_update_end, int nc, int ns, const size_t* bounds, const int* classes) {
+        if (nc == 0) {          // back to the two parameter groups (graphs captured for them were never dropped)
+            n_classes = 0; seg_bounds.clear(); seg_class.clear(); class_vals.clear();
+            return MB_OK;
+        }
+        if (nc < 0 || nc > MB_CLASSES_MAX || ns < 1 || ns > MB_SEGMENTS_MAX || !bounds || !classes) return MB_ERR_ARG;
+        if (bounds[0] != 0 || bounds[ns] != n_update_end) return MB_ERR_SHAPE;
+        for (int s = 0; s < ns; ++s) {
+            if (bounds[s + 1] <= bounds[s]) return MB_ERR_SHAPE;
+            if (classes[s] < 0 || classes[s] >= nc) return MB_ERR_ARG;
+            bool at_tensor = false;
+            for (const auto& t : tensors) if (t.off == bounds[s]) { at_tensor = true; break; }
+            if (!at_tensor) return MB_ERR_SHAPE;
+        }
+        const bool same = nc == n_classes && (int)seg_class.size() == ns && std::equal(classes, classes + ns, seg_class.begin()) &&
+                          std::equal(bounds, bounds + ns + 1, seg_bounds.begin());
+        if (same) return MB_OK;
+        n_classes = nc; seg_bounds.assign(bounds, bounds + ns + 1); seg_class.assign(classes, classes + ns); class_vals.clear();
+        if (++map_version <= 0) map_version = 1;
+        return MB_OK;
+    }
+    int set_update_values(int nc, const float* lr, const float* beta1, const float* beta2, const float* eps, const float* weight_decay,
+                          const int* correct_bias) {
+        if (nc < 1 || nc != n_classes || !lr || !beta1 || !beta2 || !eps || !weight_decay || !correct_bias) return MB_ERR_ARG;
+        class_vals.resize((size_t)nc);
+        for (int c = 0; c < nc; ++c) class_vals[c] = ClassVals{lr[c], beta1[c], beta2[c], eps[c], weight_decay[c], correct_bias[c]};
+        return MB_OK;
+    }
+    int update_stats(size_t* ridden, size_t* swept, int* segments) const {
+        if (ridden) *ridden = upd_ridden;
+        if (swept) *swept = upd_swept;
+        if (segments) *segments = upd_segments;
+        return MB_OK;
+    }
+    // riders of a classed step: a slice that ends at element `top` (exclusive) may reach down to the start of the segment that holds
+    // top - 1, and reads that segment's class
+    void ride_segment(size_t top, size_t* floor, int* cls) const {
+        const size_t s = (size_t)(std::upper_bound(seg_bounds.begin(), seg_bounds.end(), top - 1) - seg_bounds.begin()) - 1;
+        *floor = seg_bounds[s]; *cls = seg_class[s];
+    }
+    // the sweep of a classed step: [b0, e0) and [b1, e1) (ascending, disjoint) cut at the segment boundaries
+    int sweep_pieces(AdamPieces& out, size_t b0, size_t e0, size_t b1, size_t e1) const {
+        out = AdamPieces{};
+        const size_t rb[2] = {b0, b1}, re[2] = {e0, e1};
+        size_t total4 = 0;
+        for (int r = 0; r < 2; ++r)
+            for (size_t s = 0; s + 1 < seg_bounds.size(); ++s) {
+                const size_t lo = std::max(rb[r], seg_bounds[s]), hi = std::min(re[r], seg_bounds[s + 1]);
+                if (lo >= hi) continue;
+                if (out.count >= MB_SWEEP_PIECES_MAX) return MB_ERR_ARG;
+                if ((lo | hi) % 4 || hi / 4 > 0xffffffffull || total4 + (hi - lo) / 4 > 0xffffffffull) return MB_ERR_SHAPE;
+                out.begin4[out.count] = (uint32_t)(lo / 4); out.start4[out.count] = (uint32_t)total4; out.slot[out.count] = (uint8_t)seg_class[s];
+                total4 += (hi - lo) / 4;
+                out.start4[++out.count] = (uint32_t)total4;
+            }
+        return MB_OK;
+    }
     uint32_t* key_state(char* ws) const { return (uint32_t*)(ws + ws_state + 2 * sizeof(AdamArgs)); }
     DropKey step_key(char* ws, bool training, uint64_t seed, uint64_t step, uint32_t site, float p) const {
         if (!training) return kNoDrop;
@@ -454,6 +533,11 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
                            int opt_step, int correct_bias, float grad_scale, float loss_scale, int mode, bool force_launches,
                            hipStream_t st, Enqueue enqueue_inner, int nseg = 1, Between between = Between(), int variant = 0,
                            const void* tag = nullptr, int (*verify)(const void* tag, int nseg, int sg, hipGraph_t gr) = nullptr) {
+    if (m && e->n_classes > 0 && (int)e->class_vals.size() != e->n_classes) return MB_ERR_ARG;      // a map without this step's values
+    // (a micro-step without the optimizer enqueues the same kernels under any map; data-parallel variants are positive, and refuse a map)
+    if (m && e->n_classes > 0 && variant == 0) variant = -e->map_version;
+    e->upd_ridden = e->upd_swept = 0; e->upd_segments = 0;
+    if (m && e->n_classes > 0) CK(e->ensure_class_table());
     // The step may be cut into `nseg` segments: enqueue_inner(seg, ...) issues the kernels of one (captured and replayed as its own
     // LINEAR graph), between(seg, st) runs on the host right after segment `seg` was enqueued and is never captured -- the place for
     // cross-stream events (a graph with a fork inside runs on ROCm 7.2's slow path; a chain of linear graphs does not).
@@ -505,6 +589,16 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
         a.weight_decay = 0.f;
         pa.adam[1] = a;
         pa.adam_dst = e->adam_state(ws);
+        for (int c = 0; c < e->n_classes; ++c) {          // classed step: every class's scalars, derived the same way
+            const auto& cv = e->class_vals[c];
+            double cs = cv.lr;
+            if (cv.correct_bias) cs = (double)cv.lr * sqrt(1.0 - pow((double)cv.beta2, (double)opt_step)) / (1.0 - pow((double)cv.beta1, (double)opt_step));
+            AdamArgs k;
+            k.lr = cv.lr; k.beta1 = cv.beta1; k.beta2 = cv.beta2; k.eps = cv.eps; k.weight_decay = cv.weight_decay; k.step_size = (float)cs;
+            k.grad_scale = grad_scale;
+            pa.cls[c] = k;
+        }
+        if (e->n_classes > 0) { pa.ncls = e->n_classes; pa.cls_dst = e->class_state(ws); }
     }
     CK(step_prologue(pa, st));
     if (mode == 2 || force_launches) {
@@ -545,6 +639,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
             if (r3) { mb::ck_trace("hipGraphInstantiate", __FILE__, __LINE__, r3); hipGraphDestroy(gr); ng.destroy(); return r3; }
             ng.graph.push_back(gr); ng.exec.push_back(ex);
         }
+        ng.ridden = e->upd_ridden; ng.swept = e->upd_swept; ng.segments = e->upd_segments;
         e->graphs.push_back(ng);
         g = &e->graphs.back();
         ++e->graph_captures;
@@ -554,6 +649,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
         CK(between(sg, st));
     }
     ++e->graph_launches;
+    e->upd_ridden = g->ridden; e->upd_swept = g->swept; e->upd_segments = g->segments;
     flags.ok = true;
     return MB_OK;
 }

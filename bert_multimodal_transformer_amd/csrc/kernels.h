@@ -309,12 +309,23 @@ struct AdamRanges { size_t begin[MB_SWEEP_MAX], n[MB_SWEEP_MAX]; int slot[MB_SWE
 struct WordSkip { const uint32_t* stamp; const uint32_t* state; size_t begin, end; uint32_t row_len; };
 int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const AdamRanges& r, size_t n_decay, size_t sh_begin, size_t sh_end,
                 size_t keep_begin, size_t keep_end, const AdamArgs* dyn, const WordSkip& skip, hipStream_t st);
+// Update classes (include/magbert_hip.h: mb_*_set_update_map): one optimizer parameter group's scalars per slot of a table in device
+// memory, and the flat layout cut into segments -- maximal runs of tensors of one class.  The sweep of a classed step is ONE launch over
+// a table of pieces (what the riders left, cut at the segment boundaries): piece k covers quads [begin4[k], begin4[k] + start4[k + 1] -
+// start4[k]) of the buffers, start4 being the running sum of the pieces' lengths, and reads its scalars from cls[slot[k]].  The class's
+// own weight_decay decides whether a piece decays (no n_decay here).  Same per-element arithmetic as adamw_sweep: the same bits.
+#define MB_CLASSES_MAX 32
+#define MB_SEGMENTS_MAX 128
+#define MB_SWEEP_PIECES_MAX (MB_SEGMENTS_MAX + 2)
+struct AdamPieces { uint32_t begin4[MB_SWEEP_PIECES_MAX], start4[MB_SWEEP_PIECES_MAX + 1]; uint8_t slot[MB_SWEEP_PIECES_MAX]; int count; };
+int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
+                        size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------ step prologue (rowops.hip)
 // Everything that changes from one optimizer step to the next, moved into device memory by ONE small launch so that the rest
 // of the step can be a replayed hipGraph: the six batch tensors (gathered into the engine's fixed staging buffers), the
 // dropout keys of every site for (seed, step) -- same derivation as make_key() on the host -- and the AdamW scalars of the
-// two parameter groups (lr, bias-corrected step size, gradient scale).
+// two parameter groups (lr, bias-corrected step size, gradient scale), or of every update class of a classed step.
 #define MB_PROLOGUE_MAX_COPIES 8
 struct PrologueArgs {
     const uint32_t* src[MB_PROLOGUE_MAX_COPIES]; uint32_t* dst[MB_PROLOGUE_MAX_COPIES]; uint32_t dwords[MB_PROLOGUE_MAX_COPIES];
@@ -322,6 +333,7 @@ struct PrologueArgs {
     uint64_t seed, step;
     uint32_t* keys; int nsites;            // keys[2 * site + {0, 1}]
     AdamArgs adam[2]; AdamArgs* adam_dst;  // may be null
+    AdamArgs cls[MB_CLASSES_MAX]; AdamArgs* cls_dst; int ncls;      // update classes of a classed step: cls_dst[0 .. ncls) = cls (cls_dst may be null)
     uint32_t* zero_dw;                     // one dword cleared by the launch (the step's loss accumulator), may be null
     // modality tensors packed on the way in: src fp32 [rows][cols] (device or pinned host) -> dst [rows][pitch] of `dtype` (MAG's
     // GEMM operands; columns [cols, pitch) are never written and stay zero) -- what pack_pad does, without its two launches
@@ -336,6 +348,7 @@ struct PrologueArgs {
     struct MagPackW { const float* W_hv; const float* W_ha; const float* W_v; const float* W_a; void* We; void* Wv; void* Wa; MagDims d; int dtype; } magw;
     int copy_blocks;
 };
+static_assert(sizeof(PrologueArgs) <= 2048, "PrologueArgs travels as kernel arguments (4 KB limit)");
 int step_prologue(const PrologueArgs& a, hipStream_t st);
 // p[0, bytes) = 0 as a kernel launch (bytes and p multiples of 4); up to MB_ZERO_MAX ranges in one launch
 #define MB_ZERO_MAX 8

@@ -780,6 +780,7 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
             a.keys[2 * s + 1] = (uint32_t)(h >> 32);
         }
         if (a.adam_dst && threadIdx.x < 2) a.adam_dst[threadIdx.x] = a.adam[threadIdx.x];
+        if (a.cls_dst && (int)threadIdx.x < a.ncls) a.cls_dst[threadIdx.x] = a.cls[threadIdx.x];
     }
     if (tid == 0 && a.zero_dw) *a.zero_dw = 0u;
     // occurrences of every token id of this batch (a vocab-sized table that is all zero between steps): the embedding backward adds
@@ -856,7 +857,7 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
 
 int step_prologue(const PrologueArgs& a, hipStream_t st) {
     if (a.ncopies < 0 || a.ncopies > MB_PROLOGUE_MAX_COPIES || a.nsites < 0 || (a.nsites > 0 && !a.keys)) return MB_ERR_ARG;
-    if (a.npack < 0 || a.npack > 2) return MB_ERR_ARG;
+    if (a.npack < 0 || a.npack > 2 || a.ncls < 0 || a.ncls > MB_CLASSES_MAX) return MB_ERR_ARG;
     if (a.stamp && (!a.stamp_state || !a.ids)) return MB_ERR_ARG;
     size_t most = 0;
     for (int k = 0; k < a.npack; ++k) {

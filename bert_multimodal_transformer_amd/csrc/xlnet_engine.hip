@@ -251,6 +251,7 @@ void mb_xlnet_destroy(mb_xlnet_engine* e) {
     if (!e) return;
     e->destroy_prof();
     e->drop_graphs();
+    e->free_class_table();
     delete e;
 }
 int mb_xlnet_num_tensors(const mb_xlnet_engine* e) { return (int)e->tensors.size(); }
@@ -411,12 +412,20 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
     auto take_ride = [&](int l, size_t budget, int blocks) -> AdamRide {
         AdamRide r = {};
         if (!e->ride_m || !e->ride_v || l + 1 >= NL || blocks < 8 || e->ride_cursor <= e->lo[l + 1].q) return r;
-        const size_t take = std::min(e->ride_cursor - e->lo[l + 1].q, budget) / 1024 * 1024;
+        // classed step (StepMixin::n_classes): the slice stays inside the segment that holds its top element and reads that class's slot
+        size_t floor = e->lo[l + 1].q;
+        const AdamArgs* dyn = e->adam_state(ws);
+        if (e->n_classes > 0) {
+            size_t sb = 0; int cl = 0;
+            e->ride_segment(e->ride_cursor, &sb, &cl);
+            floor = std::max(floor, sb); dyn = e->class_state(ws) + cl;
+        }
+        const size_t take = std::min(e->ride_cursor - floor, budget) / 1024 * 1024;
         const size_t re = e->ride_cursor, rb = re - take;
         const bool sh_ok = dt != DT_BF16 || (e->sh_begin <= rb && re <= e->sh_end);
         if (take == 0 || rb % 4 || !sh_ok) return r;
         const bool keep = e->keep_in_step() && e->stale_begin <= rb && re <= e->stale_end;
-        r = AdamRide{P + rb, G + rb, e->ride_m + rb, e->ride_v + rb, dt == DT_BF16 ? (bf16*)(e->SH + rb * 2) : nullptr, take / 4, e->adam_state(ws),
+        r = AdamRide{P + rb, G + rb, e->ride_m + rb, e->ride_v + rb, dt == DT_BF16 ? (bf16*)(e->SH + rb * 2) : nullptr, take / 4, dyn,
                      blocks / 8 * 8, keep ? 0 : 1};
         e->ride_cursor = rb;
         return r;
@@ -611,7 +620,21 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
     const int rb = mb_xlnet_backward(e, nullptr, lab, loss_scale, 0, e->c.n_layer + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
-    if (m && v && ride) {
+    if (m && v) {
+        e->upd_ridden = ride ? e->wsum - e->ride_cursor : 0; e->upd_swept = e->n_trainable - e->upd_ridden;
+        e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
+    }
+    if (m && v && e->n_classes > 0) {
+        // Classed step (kernels.h AdamPieces): what the riders left and the rest of both slabs, cut at the segment boundaries, every piece
+        // with its class's slot, as ONE launch
+        AdamPieces pieces;
+        CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wsum, e->wsum, e->n_trainable));
+        const bool keep = e->keep_in_step();
+        CK(e->prof_mark(2 * e->c.n_layer, st));
+        CK(adamw_sweep_classed(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, pieces, e->sh_begin, e->sh_end,
+                               keep ? e->stale_begin : 0, keep ? e->stale_end : 0, e->class_state(ws), WordSkip{}, st));
+        CK(e->prof_mark(2 * e->c.n_layer + 1, st));
+    } else if (m && v && ride) {
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_trainable;
         CK(e->prof_mark(2 * e->c.n_layer, st));
@@ -631,6 +654,20 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
         CK(e->prof_mark(2 * e->c.n_layer + 1, st));
     }
     return MB_OK;
+}
+
+int mb_xlnet_set_update_map(mb_xlnet_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_map(e->tensors, e->n_trainable, n_classes, n_segments, boundaries, classes);
+}
+int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                               const float* weight_decay, const int* correct_bias) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_values(n_classes, lr, beta1, beta2, eps, weight_decay, correct_bias);
+}
+int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments) {
+    if (!e) return MB_ERR_ARG;
+    return e->update_stats(ridden, swept, segments);
 }
 
 int mb_xlnet_train_step(mb_xlnet_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
@@ -733,6 +770,7 @@ int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const f
                            float beta1, float beta2, float eps, float weight_decay, int opt_step, int correct_bias, float grad_scale,
                            float loss_scale, int mode, void* stream, mb_comm* comm) {
     hipStream_t st = (hipStream_t)stream;
+    if (e && e->n_classes > 0) return MB_ERR_MODE;          // update classes: the single-process step only
     if (!e || !e->P || !e->G || !e->ws || !comm) return MB_ERR_ARG;
     const mb_xlnet_config& c = e->c;
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;

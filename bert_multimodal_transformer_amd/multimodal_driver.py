@@ -33,7 +33,7 @@ from torch.utils.data import DataLoader, TensorDataset
 
 from .bert import BertConfig, MAG_BertForSequenceClassification
 from .global_configs import DATASET_DIMS
-from .optimization import AdamW, get_linear_schedule_with_warmup
+from .optimization import AdamW, get_linear_schedule_with_warmup, layerwise_lr_groups
 
 args = None
 DEVICE = None      # resolved in main() / _device(): the current ROCm device (reference: cuda:0, global_configs.py:7)
@@ -113,6 +113,12 @@ def get_parser():
                         help="pack every batch into a pinned host block the GPU reads in place (prefetch.PinnedBatchRing) instead of "
                              "six t.to(DEVICE) copies per step")
     parser.add_argument("--pretrained", type=str, default="", help="local checkpoint dir/file (offline)")
+    parser.add_argument("--layer_lr_decay", type=float, default=1.0,
+                        help="layer-wise learning-rate decay: layer l of N trains at learning_rate * decay ** (N - l), the embeddings "
+                             "one step below layer 0 (optimization.layerwise_lr_groups); 1.0 = off")
+    parser.add_argument("--head_learning_rate", type=float, default=None,
+                        help="learning rate of the freshly initialised parameters (MAG, pooler, classifier / sequence summary, "
+                             "logits projection); default: learning_rate")
     return parser
 
 
@@ -407,7 +413,14 @@ def prep_for_training(num_train_optimization_steps: int):
             model = MAG_XLNetForSequenceClassification(xlnet_config(args.model), multimodal_config, visual_dim=V,
                                                        acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     model.to(_device())
-    optimizer = AdamW(optimizer_grouped_parameters(model), lr=args.learning_rate)
+    if args.layer_lr_decay != 1.0 or args.head_learning_rate is not None:
+        # per-group learning rates: still ONE engine call per optimizer step (update classes, optimization.AdamW.flat_step_args)
+        n_layers = model.config.num_hidden_layers if args.model in BERT_MODELS else model.config.n_layer
+        groups = layerwise_lr_groups(model.named_parameters(), n_layers, args.learning_rate, layer_decay=args.layer_lr_decay,
+                                     head_lr=args.head_learning_rate)
+    else:
+        groups = optimizer_grouped_parameters(model)
+    optimizer = AdamW(groups, lr=args.learning_rate)
     scheduler = get_linear_schedule_with_warmup(
         optimizer, num_warmup_steps=args.warmup_proportion * num_train_optimization_steps,
         num_training_steps=num_train_optimization_steps)

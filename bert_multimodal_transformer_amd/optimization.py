@@ -13,6 +13,91 @@ import torch
 
 from . import _lib
 
+# limits of the engines' update-class table and segment map (include/magbert_hip.h)
+UPDATE_CLASSES_MAX = 32
+UPDATE_SEGMENTS_MAX = 128
+
+
+def plan_update_segments(tensors, group_of_tensor, n_update_end):
+    """The segment map of a classed single-call step (include/magbert_hip.h: mb_*_set_update_map), from the flat layout alone.
+
+    tensors: the layout's table, (name, offset, numel, ...) per tensor (_Core.tensors); group_of_tensor: per tensor the index of the
+    one parameter group that holds it, None for a tensor no group holds, or a collection of indices when several do; tensors at or
+    behind n_update_end (frozen slots) are not looked at.  Returns (boundaries, classes): segment s = [boundaries[s],
+    boundaries[s + 1]) -- a maximal run of consecutive tensors of one group, the alignment gap behind a tensor included -- belongs to
+    group classes[s]; boundaries are tensor offsets, from 0 to n_update_end.  None when a tensor below n_update_end is not in
+    exactly one group, the tensors do not tile [0, n_update_end), or there are more than UPDATE_CLASSES_MAX groups or
+    UPDATE_SEGMENTS_MAX segments."""
+    if len(tensors) != len(group_of_tensor):
+        return None
+    rows = sorted((int(t[1]), int(t[2]), g) for t, g in zip(tensors, group_of_tensor) if int(t[1]) < n_update_end)
+    boundaries, classes = [], []
+    cursor = 0
+    for off, numel, g in rows:
+        if isinstance(g, (list, tuple, set, frozenset)):
+            if len(g) != 1:
+                return None
+            g = next(iter(g))
+        if g is None or off != cursor or numel < 1:
+            return None
+        cursor = (off + numel + 63) // 64 * 64          # tensors are 64-float aligned in the flat layout
+        if not classes or classes[-1] != g:
+            boundaries.append(off)
+            classes.append(int(g))
+    if cursor != n_update_end or not classes:
+        return None
+    boundaries.append(int(n_update_end))
+    if len(set(classes)) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
+        return None
+    return boundaries, classes
+
+
+_NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")          # multimodal_driver.py:336
+_HEAD_MARKS = ("MAG.", "pooler.", "classifier.", "sequence_summary.", "logits_proj.")
+
+
+def _depth_of(name, num_layers):
+    """0 = embeddings (and any other encoder parameter), l + 1 = layer l, num_layers + 1 = the new parameters (MAG, pooler, heads)"""
+    for mark in ("encoder.layer.", "transformer.layer."):
+        at = name.find(mark)
+        if at >= 0:
+            return int(name[at + len(mark):].split(".")[0]) + 1
+    if any(name.startswith(mk) or ("." + mk) in name for mk in _HEAD_MARKS):
+        return num_layers + 1
+    return 0
+
+
+def layerwise_lr_groups(named_parameters, num_layers, lr, layer_decay=1.0, head_lr=None, weight_decay=0.01):
+    """Parameter groups for AdamW with layer-wise learning-rate decay and / or a learning rate of their own for the new parameters.
+
+    named_parameters: (name, parameter) pairs.  Depth 0 = the embeddings, depth l + 1 = `encoder.layer.l.` (BERT) / `transformer.layer.l.`
+    (XLNet, its per-layer relative-attention biases included), any other encoder parameter goes with the embeddings; depth d trains at
+    lr * layer_decay ** (num_layers + 1 - d).  The new parameters -- MAG.*, the pooler, classifier, sequence_summary, logits_proj --
+    train at head_lr (lr when None).  Every learning rate is split by the reference's no-decay rule (multimodal_driver.py:336: bias,
+    LayerNorm.bias, LayerNorm.weight in the name); empty groups are dropped.  With layer_decay == 1.0 and head_lr None the result is
+    exactly multimodal_driver.optimizer_grouped_parameters(): two groups without an lr of their own."""
+    named = list(named_parameters)
+    is_nd = lambda n: any(nd in n for nd in _NO_DECAY)
+    if layer_decay == 1.0 and head_lr is None:
+        return [{"params": [p for n, p in named if not is_nd(n)], "weight_decay": weight_decay},
+                {"params": [p for n, p in named if is_nd(n)], "weight_decay": 0.0}]
+    buckets = {}
+    for n, p in named:
+        d = _depth_of(n, num_layers)
+        if d < 0 or d > num_layers + 1:
+            raise ValueError("parameter %s names layer %d of a model of %d layers" % (n, d - 1, num_layers))
+        buckets.setdefault((d, is_nd(n)), []).append(p)
+    groups = []
+    for d in range(num_layers + 2):
+        if d == num_layers + 1:
+            lr_d = lr if head_lr is None else head_lr
+        else:
+            lr_d = lr * layer_decay ** (num_layers + 1 - d)
+        for nd in (False, True):
+            if buckets.get((d, nd)):
+                groups.append({"params": buckets[(d, nd)], "weight_decay": 0.0 if nd else weight_decay, "lr": lr_d})
+    return groups
+
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
@@ -27,6 +112,7 @@ class AdamW(torch.optim.Optimizer):
         self.grad_scale = 1.0          # data parallel: 1/world_size when gradients were SUM-reduced
         self.fused_zero_grad = True    # clear gradients inside the update kernel (zero_grad() then costs nothing)
         self._plan = None
+        self._class_maps = {}          # per flat buffer: the segment map of a classed single-call step (flat_step_args), or None
         self._t = 0
         self._dp = None              # set by distributed.DataParallel
 
@@ -79,11 +165,34 @@ class AdamW(torch.optim.Optimizer):
             if covered:
                 core.mark_grads_zero(True)
 
+    def _class_map(self, core):
+        """(boundaries, classes, groups) of this optimizer's groups over `core`'s flat layout -- the segment map of a classed step and
+        the parameter group behind every class -- or None (plan_update_segments).  The plan is fixed, so this is computed once."""
+        if id(core) not in self._class_maps:
+            owner = {}
+            for gi, group in enumerate(self.param_groups):
+                for p in group["params"]:
+                    info = getattr(p, "_mb_flat", None)
+                    if info is not None and info[0] is core:
+                        owner.setdefault(info[1], set()).add(gi)
+            n_end = getattr(core, "n_update_end", core.n_params)
+            planned = plan_update_segments(core.tensors, [owner.get(t[1]) for t in core.tensors], n_end)
+            if planned is not None:
+                groups = sorted(set(planned[1]))
+                planned = (planned[0], [groups.index(g) for g in planned[1]], groups)
+            self._class_maps[id(core)] = planned
+        return self._class_maps[id(core)]
+
     def flat_step_args(self, core, allow_dp=False):
-        """Hyper-parameters of step() as ONE whole-buffer update, when this optimizer is exactly the driver's two parameter
-        groups (multimodal_driver.py:329-343) over `core`'s flat buffer: [0, n_decay) decayed, the rest not, same lr / betas /
-        eps / bias correction in both.  None otherwise (loose tensors, more groups, diverged groups, data parallel): the caller
-        then runs step() as usual.  Used by the whole-step graph (mb_bert_train_step), which applies the update itself."""
+        """Hyper-parameters of step() as ONE whole-buffer update.  When this optimizer is exactly the driver's two parameter groups
+        (multimodal_driver.py:329-343) over `core`'s flat buffer -- [0, n_decay) decayed, the rest not, same lr / betas / eps / bias
+        correction in both -- the scalars of that update.  For any other set of groups that covers the buffer's trainable range exactly
+        once: the same dictionary with "map" = (boundaries, classes), the segment map (plan_update_segments), and "classes" = the
+        per-class lists lr / beta1 / beta2 / eps / weight_decay / correct_bias of this step (include/magbert_hip.h:
+        mb_*_set_update_map / _set_update_values).  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
+        segments than the engine takes, fused_zero_grad off, data parallel -- whose step keeps its Python-driven exchange for classed
+        optimizers, allow_dp or not): the caller then runs step() as usual.  Used by the whole-step graph (mb_bert_train_step), which
+        applies the update itself."""
         if (self._dp is not None and not allow_dp) or not self.fused_zero_grad:
             return None
         if self._plan is None:
@@ -92,6 +201,21 @@ class AdamW(torch.optim.Optimizer):
         loose = [it for it in self._plan if it[0] != "flat"]
         if any(it[2].grad is not None for it in loose):           # grad-less parameters (MAG-XLNet's frozen mask_emb) are skipped by step() too
             return None
+        two = self._two_group_args(core, flats)
+        if two is not None or self._dp is not None or not flats or any(it[2] is not core for it in flats):
+            return two
+        planned = self._class_map(core)
+        if planned is None:
+            return None
+        boundaries, classes, groups = planned
+        gs = [self.param_groups[g] for g in groups]
+        return dict(m=core._adam_m, v=core._adam_v, grad_scale=float(self.grad_scale), map=(boundaries, classes),
+                    classes=dict(lr=[float(g["lr"]) for g in gs], beta1=[float(g["betas"][0]) for g in gs],
+                                 beta2=[float(g["betas"][1]) for g in gs], eps=[float(g["eps"]) for g in gs],
+                                 weight_decay=[float(g["weight_decay"]) for g in gs],
+                                 correct_bias=[1 if g["correct_bias"] else 0 for g in gs]))
+
+    def _two_group_args(self, core, flats):
         if len(flats) != 2 or any(it[2] is not core for it in flats):
             return None
         (_, g0, _, a0, b0), (_, g1, _, a1, b1) = sorted(flats, key=lambda it: it[3])

@@ -277,6 +277,31 @@ int mb_bert_load_batch(mb_bert_engine* e, const int64_t* input_ids, const float*
 /* number of graphs captured / replays launched so far (tests, bench) */
 int mb_bert_graph_stats(const mb_bert_engine* e, size_t* captures, size_t* launches);
 
+/* Update classes: per-group AdamW hyper-parameters in mb_bert_train_step (a larger learning rate for the new parameters, layer-wise
+ * learning-rate decay, ...).  An update CLASS is one optimizer parameter group's lr / beta1 / beta2 / eps / weight_decay /
+ * correct_bias; a SEGMENT is a run of consecutive tensors of the flat layout that belong to one class.
+ * set_update_map: segment s covers elements [boundaries[s], boundaries[s + 1]) and belongs to class classes[s] (n_segments + 1
+ *   boundaries, n_segments classes; host memory, copied).  The boundaries must be tensor offsets (mb_bert_tensor_info), ascending, from 0
+ *   to mb_bert_param_count (MAG-XLNet: mb_xlnet_trainable_count) -- MB_ERR_SHAPE otherwise; more than MB_UPDATE_CLASSES_MAX classes or
+ *   MB_UPDATE_SEGMENTS_MAX segments, or a class outside [0, n_classes): MB_ERR_ARG.  A refused map leaves the previous one in force.
+ *   n_classes = 0 (the other arguments are ignored) clears the map: the step of the two parameter groups again, the default.  The map is
+ *   part of the identity of a captured step graph (rider slices and the sweep are cut at the segment boundaries); installing the map
+ *   that is already in force changes nothing.
+ * set_update_values: the hyper-parameters of every class (arrays of n_classes, which must be the map's; host memory, copied) that the
+ *   following mb_bert_train_step calls consume, until the next call.  With a map set the scalar lr .. weight_decay and correct_bias arguments of the
+ *   step are ignored -- opt_step, grad_scale and loss_scale are used as ever -- and inside a segment the class's own weight_decay decides
+ *   whether it decays, not the slab.  A step that ends with the optimizer (m, v given) while a map without values is set returns MB_ERR_ARG.
+ *   New values never re-capture a graph: they reach the device with the step prologue, as the two groups' scalars do.
+ * update_stats: the last enqueued update -- elements updated by riders inside the backward launches, elements updated by the sweep at the
+ *   end of the step, and the number of segments of the map it ran under (0: the two parameter groups).  Any pointer may be NULL.
+ * While a map is set MB_ADAMW_IN_WGRAD and MB_ADAMW_OVERLAP are off and mb_bert_train_step_dp returns MB_ERR_MODE. */
+#define MB_UPDATE_CLASSES_MAX 32
+#define MB_UPDATE_SEGMENTS_MAX 128
+int mb_bert_set_update_map(mb_bert_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes);
+int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                              const float* weight_decay, const int* correct_bias);
+int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments);
+
 /* Measurement hooks (bench.py): with profiling on, every per-layer grouped weight-gradient launch of mb_bert_backward is
  * bracketed by HIP timing events on the engine's internal side stream -- the stream that kernel runs on, which the
  * caller cannot see.  mb_bert_profile_wgrad_us waits for the last backward's events and returns the mean launch
@@ -444,6 +469,12 @@ int mb_xlnet_load_batch(mb_xlnet_engine* e, const int64_t* input_ids, const floa
                         const void** staged6, void* stream);
 int mb_xlnet_graph_stats(const mb_xlnet_engine* e, size_t* captures, size_t* launches);
 size_t mb_xlnet_trainable_count(const mb_xlnet_engine* e);
+/* update classes of mb_xlnet_train_step: as mb_bert_set_update_map / _set_update_values / _update_stats above; the map covers
+ * [0, mb_xlnet_trainable_count), and the sweep of a classed step is one launch here too */
+int mb_xlnet_set_update_map(mb_xlnet_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes);
+int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                               const float* weight_decay, const int* correct_bias);
+int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments);
 
 /* ------------------------------------------------------------------------------------------------ data parallel (new)
  * The reference is single-device (global_configs.py:4,7; multimodal_driver.py:21 imports a DistributedSampler it never uses).

@@ -12,6 +12,9 @@
 //            (mb_comm_unique_id / mb_comm_create_rccl): the N > 1 code path -- graph chain, comm stream, events, ncclAllReduce /
 //            ncclAllGather calls, the row-wise word-embedding exchange -- without a second GPU.  Needs --graph 1|2.
 //   --graph: 0 forward/backward/AdamW calls, 1 mb_bert_train_step hipGraph replay, 2 mb_bert_train_step stream launches
+//   --layer_decay D, --head_lr_mult K (each off at 1; --graph 1|2, no --dp): per-group learning rates as update classes
+//            (mb_*_set_update_map / _set_update_values) -- layer l of N at lr * D^(N - l), the embeddings at lr * D^(N + 1), MAG / pooler /
+//            heads at K * lr, every learning rate split by the no-decay rule while that fits the class table (one class per depth otherwise)
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
 // Prints one line per run: ms/step (HIP events around the K timed steps), host enqueue ms/step, samples/s, final loss.
@@ -39,6 +42,7 @@ struct Batch { int64_t *ids, *seg, *mask; float *vis, *aco, *lab; };
 int main(int argc, char** argv) {
     int steps = 30, warmup = 5, B = 48, L = 50, V = 47, A = 74, layers = 12, graph = 0, h2d = 0, nbatch = 4, dtype = MB_DT_BF16;
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
+    double layer_decay = 1.0, head_lr_mult = 1.0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -49,9 +53,10 @@ int main(int argc, char** argv) {
         else if (k == "--shard") shard = atoi(v);
         else if (k == "--hidden") hidden = atoi(v); else if (k == "--heads") heads = atoi(v); else if (k == "--inter") inter = atoi(v);
         else if (k == "--model") xl = strcmp(v, "xlnet") == 0;       // MAG-XLNet (BASELINE.json configs[3]): the single-call step only (--graph 1|2)
+        else if (k == "--layer_decay") layer_decay = atof(v); else if (k == "--head_lr_mult") head_lr_mult = atof(v);
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -143,6 +148,45 @@ int main(int argc, char** argv) {
     }
     const float lr = 1e-5f, b1 = 0.9f, b2 = 0.999f, eps = 1e-6f, wd = 0.01f;
     int t_opt = 0;
+    const bool classed = layer_decay != 1.0 || head_lr_mult != 1.0;
+    int n_classes = 0, n_segments = 0;
+    if (classed) {
+        if (!graph || dp) { fprintf(stderr, "--layer_decay / --head_lr_mult: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
+        // depth 0 = embeddings (and any other encoder tensor), l + 1 = layer l, layers + 1 = MAG / pooler / heads
+        const bool split = 2 * (layers + 2) <= MB_UPDATE_CLASSES_MAX;
+        std::vector<int> slot_of(2 * (layers + 2), -1);
+        std::vector<size_t> bounds; std::vector<int> cls;
+        std::vector<float> c_lr, c_b1, c_b2, c_eps, c_wd; std::vector<int> c_cb;
+        char name[160]; size_t off, numel; int nd_, dec; int64_t shp[4];
+        const int ntens = xl ? mb_xlnet_num_tensors(ex) : mb_bert_num_tensors(e);
+        size_t end = 0;
+        for (int i = 0; i < ntens; ++i) {           // (the table is in layout order)
+            if (xl) MCK(mb_xlnet_tensor_info(ex, i, name, 160, &off, &numel, &nd_, shp, &dec));
+            else MCK(mb_bert_tensor_info(e, i, name, 160, &off, &numel, &nd_, shp, &dec));
+            if (dec == 2) continue;                 // frozen
+            const std::string s = name;
+            int depth = 0;
+            const size_t at = s.find(".layer.");
+            if (at != std::string::npos) depth = atoi(s.c_str() + at + 7) + 1;
+            else if (s.find("MAG.") != std::string::npos || s.find("pooler.") != std::string::npos || s.find("classifier.") != std::string::npos ||
+                     s.find("sequence_summary.") != std::string::npos || s.find("logits_proj.") != std::string::npos) depth = layers + 1;
+            const bool no_decay = s.find("bias") != std::string::npos || s.find("LayerNorm.weight") != std::string::npos;
+            const int key = 2 * depth + ((split && no_decay) ? 1 : 0);
+            if (slot_of[key] < 0) {
+                slot_of[key] = n_classes++;
+                c_lr.push_back(depth == layers + 1 ? (float)(lr * head_lr_mult) : (float)(lr * pow(layer_decay, layers + 1 - depth)));
+                c_b1.push_back(b1); c_b2.push_back(b2); c_eps.push_back(eps); c_wd.push_back((split && no_decay) ? 0.f : wd); c_cb.push_back(1);
+            }
+            if (cls.empty() || cls.back() != slot_of[key]) { bounds.push_back(off); cls.push_back(slot_of[key]); }
+            end = (off + numel + 63) / 64 * 64;
+        }
+        bounds.push_back(end);
+        n_segments = (int)cls.size();
+        if (xl) { MCK(mb_xlnet_set_update_map(ex, n_classes, n_segments, bounds.data(), cls.data()));
+                  MCK(mb_xlnet_set_update_values(ex, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
+        else { MCK(mb_bert_set_update_map(e, n_classes, n_segments, bounds.data(), cls.data()));
+               MCK(mb_bert_set_update_values(e, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
+    }
     auto step = [&](int i) {
         char* src = db[i % nbatch];
         if (h2d == 1) HCK(hipMemcpyAsync(src, hb[i % nbatch], bytes, hipMemcpyHostToDevice, st));     // copy engine, same stream
@@ -189,6 +233,12 @@ int main(int argc, char** argv) {
            "%.1f samples/s last-loss %.4f mean-loss %.4f\n",
            xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, shape, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
            hl[1] / (steps + warmup));
+    if (graph && !dp) {
+        size_t ridden = 0, swept = 0; int segs = 0;
+        if (xl) MCK(mb_xlnet_update_stats(ex, &ridden, &swept, &segs)); else MCK(mb_bert_update_stats(e, &ridden, &swept, &segs));
+        printf("step_bench update: classes=%d segments=%d ridden=%zu swept=%zu (layer_decay=%g head_lr_mult=%g)\n", n_classes, segs, ridden, swept,
+               layer_decay, head_lr_mult);
+    }
     if (comm) {
         float ex = 0.f; size_t pieces = 0, cbytes = 0;
         MCK(mb_comm_exposed_ms(comm, &ex)); MCK(mb_comm_stats(comm, &pieces, &cbytes));
