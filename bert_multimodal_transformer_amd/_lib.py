@@ -52,6 +52,8 @@ PROTOTYPES = {
                                _i, _dk, _vp]),
     "mb_attention_forward": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _dk, _vp]),
     "mb_attention_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp]),
+    "mb_attention_resident_forward": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp, _vp]),
+    "mb_attention_resident_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),
     "mb_attention_tiled_stats_bytes": (_sz, [_i, _i, _i]),
     "mb_attention_tiled_forward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp, _vp]),
     "mb_attention_tiled_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),

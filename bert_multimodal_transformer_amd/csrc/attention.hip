@@ -22,6 +22,16 @@
 
 namespace mb {
 
+// The bias that every key of the sample carries: kMaskNeg when the sample has no real key at all (a fully padded sample), else 0.
+// The softmax does not depend on a bias common to all keys, but fp32 holds score / 8 - 10000 to 4.9e-4 only, so such a sample's
+// probabilities came out 4e-4 off the exact ones in fp32.  It is taken off the key biases before they are added; with one real key
+// it is 0 and x - 0 is x, the same bits as before.  Every wave works it out for itself (L <= 128: two mask words per lane).
+__device__ __forceinline__ float common_key_bias(const int64_t* __restrict__ mrow, int L, int lane) {
+    bool live = false;
+    for (int j = lane; j < L; j += 64) live |= mrow[j] != 0;
+    return __ballot(live) ? 0.0f : kMaskNeg;
+}
+
 // =============================================================================================== forward
 template <class T, int LP, int NW>
 __global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(const T* __restrict__ qkv, const int64_t* __restrict__ mask,
@@ -52,8 +62,9 @@ __global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(const T* __restrict__
         const size_t lds[3] = {ld, ld, ld};
         stage_heads<T, LP, NW * 64, 3>(img, PIT, src, lds, L);
     }
+    const float shift = common_key_bias(mask + (size_t)b * L, L, lane);
     for (int j = threadIdx.x; j < LP; j += NW * 64)
-        mbias[j] = j < L ? (1.0f - (float)mask[(size_t)b * L + j]) * kMaskNeg : kPadNeg;
+        mbias[j] = j < L ? (1.0f - (float)mask[(size_t)b * L + j]) * kMaskNeg - shift : kPadNeg;
     __syncthreads();
 
     const float scale = 0.125f;
@@ -207,8 +218,9 @@ __device__ __forceinline__ void attn_bwd_body(const T* __restrict__ qkv, const i
         const size_t lds[4] = {ld, ld, ld, (size_t)H};
         stage_heads<T, LP, NW * 64, 4>(img, PIT, src, lds, L);
     }
+    const float shift = common_key_bias(mask + (size_t)b * L, L, lane);
     for (int j = threadIdx.x; j < LP; j += NW * 64)
-        mbias[j] = j < L ? (1.0f - (float)mask[(size_t)b * L + j]) * kMaskNeg : kPadNeg;
+        mbias[j] = j < L ? (1.0f - (float)mask[(size_t)b * L + j]) * kMaskNeg - shift : kPadNeg;
     // per-lane running column sums of the dQ / dK / dV tiles this wave produces (its own row only; rows >= L excluded);
     // reduced over the 16 rows and the waves once, at the very end
     f32x4 cq[4], ck[4], cv[4];

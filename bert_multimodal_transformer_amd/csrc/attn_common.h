@@ -163,7 +163,9 @@ __device__ __forceinline__ float quad_sum(float v) {
 }
 
 constexpr float kMaskNeg = -10000.0f;     // transformers 3.0.2 get_extended_attention_mask
-constexpr float kPadNeg = -1.0e30f;       // keys beyond L (tile padding only)
+// keys beyond L (tile padding only) of the BERT kernels, whose mask value is kMaskNeg.  The XLNet kernels mask with -1e30 itself and
+// pad with -inf instead (xlnet_attention.hip kXlPad, xlnet_attention_tiled.hip)
+constexpr float kPadNeg = -1.0e30f;
 
 
 }  // namespace mb

@@ -327,6 +327,25 @@ int mb_attention_backward(int dtype, const void* qkv, const int64_t* mask, const
     return attention_backward(dtype, qkv, mask, nullptr, dctx, dqkv, (trace_on && nh <= 64) ? trace_dbias : nullptr, B, L, nh, dk(drop),
                               (hipStream_t)stream);
 }
+// the LDS-resident pair with every output its kernels have (the checks of attention_tiled.hip's tiled_check, L <= 128)
+static int resident_check(int dtype, int B, int L, int nh, const DropKey& drop) {
+    if (B < 1 || L < 1 || L > 128 || nh < 1 || (int64_t)B * nh > 0x7fffffff) return MB_ERR_SHAPE;
+    if (drop.thresh != 0u && (uint64_t)B * nh * L * L >= ((uint64_t)1 << 32)) return MB_ERR_SHAPE;
+    if (dtype != DT_BF16 && dtype != DT_F32) return MB_ERR_DTYPE;
+    return MB_OK;
+}
+int mb_attention_resident_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
+                                  const mb_dropkey* drop, const float* head_scale, float* probs, void* stream) {
+    if (int e = resident_check(dtype, B, L, nh, dk(drop))) return e;
+    if (!qkv || !mask || !ctx) return MB_ERR_ARG;
+    return attention_forward(dtype, qkv, mask, ctx, B, L, nh, dk(drop), (hipStream_t)stream, probs, head_scale);
+}
+int mb_attention_resident_backward(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, float* dbias, int B,
+                                   int L, int nh, const mb_dropkey* drop, const float* head_scale, void* stream) {
+    if (int e = resident_check(dtype, B, L, nh, dk(drop))) return e;
+    if (!qkv || !mask || !dctx || !dqkv) return MB_ERR_ARG;
+    return attention_backward(dtype, qkv, mask, nullptr, dctx, dqkv, dbias, B, L, nh, dk(drop), (hipStream_t)stream, head_scale);
+}
 size_t mb_attention_tiled_stats_bytes(int B, int L, int nh) {
     return (B < 1 || L < 1 || nh < 1) ? 0 : tiled_stats_floats(B, L, nh) * sizeof(float);
 }

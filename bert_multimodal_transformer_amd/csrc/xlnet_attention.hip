@@ -20,6 +20,10 @@
 namespace mb {
 
 constexpr float kXlMask = 1.0e30f;      // modeling_xlnet: attn_score - 1e30 * attn_mask (fp32)
+// Keys beyond L (tile padding).  Not attn_common.h's kPadNeg: -1e30 is what a masked real key scores here (score - kXlMask rounds to
+// -1e30 in fp32), so a query-stream row whose every key is masked would share its weight with the LP - L padding columns.  -inf
+// weighs nothing next to any finite maximum, and the maximum is finite: it starts at -3.0e38f and key 0 < L is a real key.
+constexpr float kXlPad = -INFINITY;
 
 struct XlParams {
     const float* r_w_bias; const float* r_r_bias; const float* r_s_bias;   // [nh][64]
@@ -183,7 +187,7 @@ __global__ void __launch_bounds__(NW * 64) xl_attn_fwd_kernel(const T* __restric
                     p = p < 0 ? 0 : (p > RWT * 16 - 1 ? RWT * 16 - 1 : p);
                     const float bd = to_f(*(const T*)(raw + (lane & 15) * RPIT + p * (int)sizeof(T)));
                     float s = (ac[jt][r] + cK[j] + bd + (si == segv[j] ? e0 : e1)) * scale;
-                    if (j >= L) s = kPadNeg;
+                    if (j >= L) s = kXlPad;
                     else if ((i != j || xp.gstream) && (padf[j] || (xp.perm != nullptr && i < L && xp.perm[((size_t)b * L + i) * L + j] != 0))) s -= kXlMask;
                     ac[jt][r] = s;
                     mx = fmaxf(mx, s);

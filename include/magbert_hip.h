@@ -94,6 +94,14 @@ int mb_attention_forward(int dtype, const void* qkv, const int64_t* mask, void* 
                          const mb_dropkey* drop, void* stream);
 int mb_attention_backward(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L,
                           int nh, const mb_dropkey* drop, void* stream);
+/* The same LDS-resident kernels with every output they have, as the engines call them.  head_scale fp32 [nh] or NULL (head_mask);
+ * probs fp32 [B][nh][L][L] or NULL: the probabilities after dropout, times head_scale (output_attentions); dbias fp32 [3H] or NULL:
+ * += the column sums of dqkv (the fused QKV bias gradient).  Arguments are checked as by the tiled pair below, except that L > 128
+ * is MB_ERR_SHAPE. */
+int mb_attention_resident_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
+                                  const mb_dropkey* drop, const float* head_scale, float* probs, void* stream);
+int mb_attention_resident_backward(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, float* dbias, int B,
+                                   int L, int nh, const mb_dropkey* drop, const float* head_scale, void* stream);
 /* The tiled kernels the engines run for 128 < L <= 512, usable at any 1 <= L <= 512 (same arithmetic; 64-row blocks streamed through
  * LDS instead of a whole sequence per head).  stats: caller scratch of mb_attention_tiled_stats_bytes(B, L, nh) -- the forward leaves
  * the row statistics of the backward in it (the backward also uses it as scratch).  head_scale fp32 [nh] or NULL (head_mask);

@@ -11,7 +11,8 @@ import torch
 from bert_multimodal_transformer_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("mb_attention_tiled_forward", "mb_attention_tiled_backward", "mb_attention_tiled_stats_bytes")
+NEW = ("mb_attention_tiled_forward", "mb_attention_tiled_backward", "mb_attention_tiled_stats_bytes",
+       "mb_attention_resident_forward", "mb_attention_resident_backward")
 
 
 def _cfg(max_seq, max_position=512, max_batch=4):
@@ -76,6 +77,35 @@ def test_tiled_launchers_check_shapes_before_pointers():
     # the LDS-resident pair keeps its L <= 128 contract
     assert L.mb_attention_forward(_lib.DT_BF16, bogus, bogus, bogus, 2, 129, 12, None, None) == 1001
     assert L.mb_attention_backward(_lib.DT_BF16, bogus, bogus, bogus, bogus, 2, 129, 12, None, None) == 1001
+
+
+def test_resident_launchers_check_shapes_before_pointers():
+    """mb_attention_resident_forward / _backward (the LDS-resident kernels with head_scale, probs and dbias): the checks of the tiled
+    pair, except that L > 128 is refused; dummy pointers, so skipped where a GPU could run a missed check"""
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    L = _lib.lib()
+    bogus = C.c_void_p(0x1000)
+    key = _lib.make_dropkey(1, 1, 17, 0.1)
+    fwd = lambda dt, B, S, nh, k: L.mb_attention_resident_forward(dt, bogus, bogus, bogus, B, S, nh, k, None, None, None)
+    bwd = lambda dt, B, S, nh, k: L.mb_attention_resident_backward(dt, bogus, bogus, bogus, bogus, None, B, S, nh, k, None, None)
+    for f in (fwd, bwd):
+        assert f(_lib.DT_BF16, 2, 129, 12, None) == 1001
+        assert f(_lib.DT_F32, 2, 512, 12, None) == 1001
+        assert f(_lib.DT_BF16, 2, 0, 12, None) == 1001
+        assert f(_lib.DT_BF16, 0, 128, 12, None) == 1001
+        assert f(_lib.DT_BF16, 2, 128, 0, None) == 1001
+        # dropout on and B * nh * L^2 >= 2^32: the uint32 mask index would wrap
+        assert f(_lib.DT_BF16, 21846, 128, 12, C.byref(key)) == 1001
+        assert f(_lib.DT_F32, 21846, 128, 12, C.byref(key)) == 1001
+        assert f(7, 2, 128, 12, None) == 1003
+    # null operands are refused after the shape (MB_ERR_ARG); the optional ones (head_scale, probs, dbias) may be null
+    assert L.mb_attention_resident_forward(_lib.DT_BF16, None, bogus, bogus, 2, 128, 12, None, None, None, None) == 1004
+    assert L.mb_attention_resident_forward(_lib.DT_BF16, bogus, None, bogus, 2, 128, 12, None, None, None, None) == 1004
+    assert L.mb_attention_resident_forward(_lib.DT_BF16, bogus, bogus, None, 2, 128, 12, None, None, None, None) == 1004
+    assert L.mb_attention_resident_backward(_lib.DT_BF16, bogus, bogus, None, bogus, None, 2, 128, 12, None, None, None) == 1004
+    assert L.mb_attention_resident_backward(_lib.DT_BF16, bogus, bogus, bogus, None, None, 2, 128, 12, None, None, None) == 1004
+    assert L.mb_attention_resident_forward(_lib.DT_BF16, None, bogus, bogus, 2, 129, 12, None, None, None, None) == 1001
 
 
 def test_tiled_kernels_registers_and_lds(tmp_path):

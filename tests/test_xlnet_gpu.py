@@ -858,6 +858,43 @@ def test_query_stream_general_mapping_and_argument_checks():
             m(ids, vis, aco, token_type_ids=seg, attention_mask=mask, target_mapping=tm_t.to(DEV))
 
 
+def _first_target_inputs(B=2, L=40, M=3):
+    """one-hot targets among the last 8 positions, a random 20 % perm_mask whose row of each sample's first target is all ones"""
+    rs = np.random.RandomState(7)
+    tm = np.zeros((B, M, L), np.float32)
+    pm = (rs.rand(B, L, L) < 0.2).astype(np.float32)
+    for bb in range(B):
+        tgt = np.sort(rs.choice(np.arange(L - 8, L), size=M, replace=False))
+        tm[bb, np.arange(M), tgt] = 1.0
+        pm[bb, tgt[0], :] = 1.0
+    return torch.from_numpy(tm), torch.from_numpy(pm)
+
+
+@pytest.mark.parametrize("cdt,tol", [(torch.float32, 1e-3), (torch.bfloat16, 1e-1)])
+def test_query_stream_first_target_attends_to_nothing(cdt, tol):
+    """The first token of a factorization order: its perm_mask row is all ones, and the query stream has no self exemption, so every
+    key of that row carries -1e30 and the reference's softmax is uniform over the L keys.  L = 40 runs the LDS-resident kernel padded
+    to 64 columns; the padding must weigh nothing there.  output_g against the oracle run live: fp32 1e-3 (as
+    test_query_stream_general_mapping_and_argument_checks), bf16 the 1e-1 of test_query_stream_matches_reference_golden.
+    With -1e30 as the pad score (the kernel before kXlPad) this case fails: output_g err 5.02e-1 in fp32 and 5.03e-1 in bf16, all of
+    it on the first targets, whose attention output came out scaled by 40 / 64 in both layers.  With -inf: 3.8e-6 and 2.4e-2."""
+    B, L, M, layers = 2, 40, 3, 2
+    m = build(layers=layers, cdt=cdt).eval()
+    o = oracle(layers=layers).eval()
+    b = weights.synthetic_xlnet_batch(B, L, 47, 74, seed=51)
+    ids, vis, aco, mask, seg, lab = tb(b, DEV)
+    tm_t, pm_t = _first_target_inputs(B, L, M)
+    with torch.no_grad():
+        got = m.transformer(ids, vis, aco, token_type_ids=seg, attention_mask=mask, perm_mask=pm_t.to(DEV), target_mapping=tm_t.to(DEV))[0].float().cpu()
+        c = tb(b)
+        want = o.transformer(c[0], c[1], c[2], c[3], c[4], perm_mask=pm_t, target_mapping=tm_t)
+    assert bool(torch.isfinite(want).all())
+    err = (got - want).abs()
+    print("query stream, first target fully masked (%s): output_g err %.2e (first targets %.2e, |g| max %.2f)"
+          % (cdt, float(err.max()), float(err[:, 0].max()), float(want.abs().max())))
+    assert tuple(got.shape) == (B, M, 768) and float(err.max()) <= tol
+
+
 @pytest.mark.parametrize("cdt", [torch.float32, torch.bfloat16])
 def test_perm_mask_gradients_vs_oracle(cdt):
     """train mode (every dropout p = 0), a random perm_mask plus ragged padding, L = 72 (two strip groups): logits and every

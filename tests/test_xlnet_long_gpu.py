@@ -21,6 +21,7 @@ from bert_multimodal_transformer_amd import (AdamW, MAG_XLNetForSequenceClassifi
 from oracle import mag_xlnet_ref as X
 from oracle import optim_ref as O
 from oracle import weights
+from attn_op_helpers import NAMES, _XlOp, _errors, _xl_ref          # noqa: F401
 from test_ops_gpu import close, rnd, stream
 from test_xlnet_gpu import DEV, LOOSE_BF16, _grad_report, oracle, tb
 
@@ -53,126 +54,7 @@ def oracle_logits(o, b, **kw):
 
 
 # ------------------------------------------------------------------------------------------------------------ op level
-def _xl_ref(qkv, kr, rwb, rrb, rsb, sege, seg, mask, perm, gstream, B, L, nh, pm):
-    """fp64: the formulas of the header of csrc/xlnet_attention_tiled.hip.  pm [B, nh, L, L]: dropout multipliers x head_scale"""
-    q, k, v = qkv.view(B, L, 3, nh, 64).permute(2, 0, 3, 1, 4)                     # [B, nh, L, 64]
-    krh = kr.view(B, 2 * L, nh, 64).permute(0, 2, 1, 3)                             # [B, nh, 2L, 64]
-    ac = (q + rwb[None, :, None, :]) @ k.transpose(-1, -2)
-    bd_full = (q + rrb[None, :, None, :]) @ krh.transpose(-1, -2)                   # [B, nh, L, 2L]
-    ar = torch.arange(L)
-    idx = (L - ar[:, None] + ar[None, :]).expand(B, nh, L, L)
-    bd = torch.gather(bd_full, -1, idx)
-    ef2 = torch.einsum("bhid,shd->bhis", q + rsb[None, :, None, :], sege)            # [B, nh, L, 2]
-    diff = (seg[:, :, None] != seg[:, None, :]).long()[:, None].expand(B, nh, L, L)
-    ef = torch.gather(ef2, -1, diff)
-    masked = (mask[:, None, :] == 0).expand(B, L, L).clone()
-    if perm is not None:
-        masked |= perm != 0
-    if not gstream:
-        masked &= ~torch.eye(L, dtype=torch.bool)[None]
-    s = (ac + bd + ef) / 8.0 - 1e30 * masked[:, None].double()
-    p = torch.softmax(s, -1)
-    vec = (p * pm) @ v
-    return vec.permute(0, 2, 1, 3).reshape(B * L, nh * 64), p
-
-
-class _XlOp(object):
-    """device tensors of one op-level case + the calls"""
-
-    def __init__(self, dt, tdt, B, L, nh, seed, p, perm=False, gstream=0):
-        self.dt, self.tdt, self.B, self.L, self.nh = dt, tdt, B, L, nh
-        H = nh * 64
-        self.qkv = rnd((B * L, 3 * H), seed, tdt, 2.0)
-        self.kr = rnd((B * 2 * L, H), seed + 1, tdt, 1.0)
-        self.dvec = rnd((B * L, H), seed + 2, tdt)
-        self.rwb, self.rrb, self.rsb = (rnd((nh, 64), seed + 3 + k, torch.float32, 0.5) for k in range(3))
-        self.sege = rnd((2, nh, 64), seed + 6, torch.float32, 0.5)
-        self.mask = torch.ones(B, L, dtype=torch.long)
-        self.mask[1, :L - 5] = 0                                             # row 1: left-padded down to 5 real keys
-        self.seg = torch.zeros(B, L, dtype=torch.long)
-        self.seg[:, L - 1] = 2
-        self.seg[0, L // 3: L // 2] = 1
-        self.seg[1, :L - 5] = 3
-        self.hs = torch.linspace(0.5, 1.5, nh, dtype=torch.float32)
-        self.hs[3] = 0.0
-        self.perm = None
-        if perm:
-            self.perm = (torch.from_numpy(np.random.RandomState(seed).rand(B, L, L) < 0.3)).to(torch.uint8)
-        self.gstream = gstream
-        if gstream:                                                          # a query row that may attend to nothing at all
-            self.perm = torch.zeros(B, L, L, dtype=torch.uint8) if self.perm is None else self.perm
-            self.perm[0, L // 2, :] = 1
-            self.perm[1, L - 2, :] = 1
-        self.key, self.pmask = None, torch.ones(B, nh, L, L, dtype=torch.float64)
-        if p > 0:
-            self.key = _lib.make_dropkey(7, 5, 16, p)
-            self.pmask = torch.from_numpy(rng.keep_mult(B * nh * L * L, rng.make_key(7, 5, 16, p))).view(B, nh, L, L).double()
-        d = lambda t, ty=None: t.to(DEV, ty) if ty is not None else t.to(DEV)
-        self.d = dict(qkv=d(self.qkv, tdt), kr=d(self.kr, tdt), dvec=d(self.dvec, tdt), rwb=d(self.rwb), rrb=d(self.rrb), rsb=d(self.rsb),
-                      sege=d(self.sege), mask=d(self.mask), seg=d(self.seg), hs=d(self.hs), perm=d(self.perm) if self.perm is not None else None)
-
-    def reference(self, backward=True):
-        leaves = [t.double().requires_grad_(backward) for t in (self.qkv, self.kr, self.rwb, self.rrb, self.rsb, self.sege)]
-        pm = self.pmask * self.hs.double()[None, :, None, None]
-        vec, _ = _xl_ref(*leaves, self.seg, self.mask, self.perm, self.gstream, self.B, self.L, self.nh, pm)
-        grads = None
-        if backward:
-            vec.backward(self.dvec.double())
-            grads = [t.grad for t in leaves]
-        return vec.detach(), grads
-
-    def _common(self):
-        d = self.d
-        return [_lib.ptr(d[k]) for k in ("qkv", "kr", "rwb", "rrb", "rsb", "sege", "seg", "mask")]
-
-    def run(self, tiled, backward=True, param_grads=True):
-        """-> vec, dqkv, dkr, (d_rwb, d_rrb, d_rsb, d_seg)"""
-        L_, d = _lib.lib(), self.d
-        dt, tdt, B, L, nh = self.dt, self.tdt, self.B, self.L, self.nh
-        H = nh * 64
-        kp = C.byref(self.key) if self.key is not None else None
-        vec = torch.zeros(B * L, H, dtype=tdt, device=DEV)
-        stats = torch.zeros(L_.mb_xlnet_attention_tiled_stats_bytes(B, L, nh) // 4, dtype=torch.float32, device=DEV)
-        es = 2 if tdt == torch.bfloat16 else 4
-        nsc = L_.mb_xlnet_attention_tiled_scratch_bytes(dt, B, L, nh) // es
-        LP = 32 if L <= 32 else (64 if L <= 64 else 128)
-        psave = None if tiled else torch.zeros(B * nh * LP * LP, dtype=tdt, device=DEV)
-        gsave = torch.zeros(max(nsc, B * nh * LP * LP), dtype=tdt, device=DEV)
-        pdsave = torch.zeros(nsc, dtype=tdt, device=DEV)
-        if tiled:
-            _lib.check(L_.mb_xlnet_attention_tiled_forward(dt, *self._common(), _lib.ptr(vec), _lib.ptr(stats), B, L, nh, kp, _lib.ptr(d["hs"]),
-                                                           _lib.ptr(d["perm"]), self.gstream, None, stream()))
-        else:
-            _lib.check(L_.mb_xlnet_attention_forward(dt, *self._common(), _lib.ptr(vec), _lib.ptr(psave), _lib.ptr(stats), B, L, nh, kp,
-                                                     _lib.ptr(d["hs"]), _lib.ptr(d["perm"]), self.gstream, stream()))
-        if not backward:
-            torch.cuda.synchronize()
-            return vec, None, None, None
-        dqkv = torch.zeros(B * L, 3 * H, dtype=tdt, device=DEV)
-        dkr = torch.zeros(B * 2 * L, H, dtype=tdt, device=DEV)
-        pg = [torch.zeros(nh, 64, device=DEV), torch.zeros(nh, 64, device=DEV), torch.zeros(nh, 64, device=DEV), torch.zeros(2, nh, 64, device=DEV)]
-        tail = [_lib.ptr(dqkv), _lib.ptr(dkr)] + [_lib.ptr(t) for t in pg] + [B, L, nh, kp, _lib.ptr(d["hs"]), _lib.ptr(d["perm"]), stream()]
-        if tiled:
-            _lib.check(L_.mb_xlnet_attention_tiled_backward(dt, *self._common(), _lib.ptr(vec), _lib.ptr(d["dvec"]), _lib.ptr(stats),
-                                                            _lib.ptr(gsave), _lib.ptr(pdsave), *tail))
-        else:
-            _lib.check(L_.mb_xlnet_attention_backward(dt, *self._common(), _lib.ptr(psave), _lib.ptr(vec), _lib.ptr(d["dvec"]), _lib.ptr(stats),
-                                                      _lib.ptr(gsave), _lib.ptr(pdsave), *tail))
-        torch.cuda.synchronize()
-        return vec, dqkv, dkr, pg
-
-
-NAMES = ("dqkv", "dkr", "d_rwb", "d_rrb", "d_rsb", "d_seg")
-
-
-def _errors(case, got, ref_vec, ref_grads):
-    """max |err| / max |ref| of every quantity"""
-    vec, dqkv, dkr, pg = got
-    out = {"vec": (vec.float().cpu(), ref_vec)}
-    if dqkv is not None:
-        for name, g, r in zip(NAMES, [dqkv, dkr] + list(pg), ref_grads):
-            out[name] = (g.float().cpu().view(r.shape), r)
-    return {k: (float((g.double() - r.double()).abs().max()), float(r.abs().max())) for k, (g, r) in out.items()}
+# (_xl_ref, _XlOp, _errors, NAMES: attn_op_helpers.py, shared with test_attention_resident_gpu.py)
 
 
 @pytest.mark.parametrize("dt,tdt", DTS)
@@ -221,7 +103,8 @@ def test_tiled_relative_attention_perm_mask_vs_fp64(dt, tdt):
 @pytest.mark.parametrize("L", [100, 300])
 def test_tiled_query_stream_mask_with_a_fully_masked_row(dt, tdt, L):
     """gstream = 1 (no self exemption): a row whose every key is masked yields the uniform distribution over the L keys -- columns
-    beyond L in the last tile must weigh nothing.  Forward only (the query stream has no backward)."""
+    beyond L in the last tile must weigh nothing.  Forward only (the query stream has no backward).  At L <= 128 the LDS-resident
+    kernels run the same inputs and every row of the two outputs is compared, the fully masked rows included."""
     case = _XlOp(dt, tdt, 2, L, 12, 31, 0.0, gstream=1)
     ref_vec, _ = case.reference(backward=False)
     vec = case.run(tiled=True, backward=False)[0]
@@ -229,10 +112,8 @@ def test_tiled_query_stream_mask_with_a_fully_masked_row(dt, tdt, L):
     v = case.qkv.double().view(2, L, 3, 12, 64)[0, :, 2].mean(0) * case.hs.double()[:, None]              # uniform over all L keys
     close(vec.float().view(2, L, 12, 64)[0, L // 2], v.float(), dt, "fully masked row", 2.0)
     if L <= 128:
-        # The LDS-resident kernels give keys beyond L the score -1e30 (attn_common.h kPadNeg), which is XLNet's mask value itself: in a
-        # fully masked row they spread the weight over LP = 128 columns instead of L and so return L / LP of the reference's row.  That
-        # is their behaviour on the parent commit too (they are not edited here); the two such rows are compared with fp64 above and
-        # left out of the kernel-against-kernel comparison, every other row is in it.
+        # the LDS-resident kernels on the same inputs: every row, the two fully masked ones included (they pad with -inf as the tiled
+        # kernels do; with -1e30, XLNet's own mask value, such a row spread its weight over LP columns and returned L / LP of this)
         res = case.run(tiled=False, backward=False)[0].float().cpu().view(2, L, 12 * 64)
         got = vec.float().cpu().view(2, L, 12 * 64)
         full = torch.zeros(2, L, dtype=torch.bool)
@@ -241,7 +122,7 @@ def test_tiled_query_stream_mask_with_a_fully_masked_row(dt, tdt, L):
         print("gstream L=%d %s: resident vs fp64 on the fully masked rows %.3e (max|ref| %.3e), tiled %.3e"
               % (L, tdt, float((res[full].double() - ref_vec.view(2, L, -1)[full]).abs().max()), float(ref_vec.view(2, L, -1)[full].abs().max()),
                  float((got[full].double() - ref_vec.view(2, L, -1)[full]).abs().max())))
-        close(got[~full], res[~full], dt, "gstream tiled vs resident", 2.0)
+        close(got, res, dt, "gstream tiled vs resident", 2.0)
 
 
 # ------------------------------------------------------------------------------------------------------------ model level
