@@ -151,6 +151,12 @@ PROTOTYPES = {
     "mb_xlnet_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
     "mb_xlnet_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mb_xlnet_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
+    "mb_grad_clip_scratch_bytes": (_sz, [_sz]),
+    "mb_grad_clip_coef": (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp]),
+    "mb_bert_set_grad_clip": (_i, [_vp, _f]),
+    "mb_bert_grad_clip_stats": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), _vp]),
+    "mb_xlnet_set_grad_clip": (_i, [_vp, _f]),
+    "mb_xlnet_grad_clip_stats": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), _vp]),
     "mb_xlnet_stage_grad_ranges": (_i, [_vp, _i, C.POINTER(_sz), C.POINTER(_sz), _i]),
     # data parallel (csrc/comm.hip)
     "mb_comm_unique_id": (_i, [_vp]),

@@ -572,6 +572,9 @@ class _Core(object):
         extra = () if comm is None else (comm.handle,)
         if opt is not None:
             self._install_update_classes(opt)
+            # gradient-norm clipping (include/magbert_hip.h: mb_*_set_grad_clip): installed with every update, 0 = off when the optimizer
+            # has no max_grad_norm, so that a second optimizer on this model cannot inherit the setting of the first
+            _lib.check(self._fn("set_grad_clip")(self.handle, float(o.get("max_grad_norm") or 0.0)))
         if self.kind == "bert" and self.grads._version != getattr(self, "_gz_version", -1):
             # torch wrote into the flat gradient buffer since the engine last looked (torch_wrote_grads): the sweep of this update
             # cannot take the word rows outside its batches for zero (include/magbert_hip.h: mb_bert_distrust_word_stamps)
@@ -607,6 +610,14 @@ class _Core(object):
             fl = lambda xs: (C.c_float * n)(*xs)
             _lib.check(self._fn("set_update_values")(self.handle, n, fl(cv["lr"]), fl(cv["beta1"]), fl(cv["beta2"]), fl(cv["eps"]),
                                                      fl(cv["weight_decay"]), (C.c_int * n)(*cv["correct_bias"])))
+
+    def grad_clip_stats(self):
+        """(norm, coef) of the last single-call update that clipped the gradient norm: the norm of the gradient as AdamW saw it, and
+        the coefficient min(1, max_norm / (norm + 1e-6)) that went into its gradient scale.  Waits for the stream; raises when clipping
+        is off or no such update has run."""
+        norm, coef = C.c_float(), C.c_float()
+        _lib.check(self._fn("grad_clip_stats")(self.handle, C.byref(norm), C.byref(coef), self.stream()))
+        return norm.value, coef.value
 
     def update_stats(self):
         """(elements updated by riders, elements updated by the end-of-step sweep, segments of the map) of the last single-call update"""
@@ -1107,6 +1118,8 @@ class _FusedStep(object):
         launches = graph == "launches" or (graph is None and os.environ.get("MB_STEP_GRAPH", "1") == "0")
         core.train_step(input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, opt, loss_scale=loss_scale,
                         mode=2 if launches else 1)
+        if opt is not None and opt.get("max_grad_norm"):
+            optimizer._clip_last = core           # (optimizer.last_grad_norm reads the engine's record when asked)
         return core.loss_buf[0]
 
     def eval_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids):

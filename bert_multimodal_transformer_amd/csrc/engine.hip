@@ -27,6 +27,7 @@ struct mb_bert_engine : StepMixin {
     size_t word, pos, type, emb_lnw, emb_lnb, wp, bp, wc, bc;
     size_t mag_whv, mag_wha, mag_wv, mag_wa, mag_bhv, mag_bha, mag_bv, mag_ba, mag_lnw, mag_lnb;
     size_t n_params, n_decay, sh_begin, sh_end;
+    size_t n_update_end() const { return n_params; }          // (StepMixin: the range an update covers, and its clipping norm)
     // workspace
     MagWs mw;
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
@@ -400,6 +401,13 @@ int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n
     return adamw_step(p, g, m, v, shadow, n, n_decay, sh_begin, sh_end, a, zero_grad, (hipStream_t)stream);
 }
 
+size_t mb_grad_clip_scratch_bytes(size_t n) { return (size_t)grad_norm_blocks(n) * sizeof(double); }
+int mb_grad_clip_coef(const float* g, size_t n, float max_norm, float grad_scale, void* scratch, float* out2, void* stream) {
+    if (!scratch || !out2) return MB_ERR_ARG;
+    CK(grad_sumsq(g, n, (double*)scratch, (hipStream_t)stream));
+    return grad_clip_finalize((const double*)scratch, grad_norm_blocks(n), nullptr, max_norm, grad_scale, out2, ClipTables{}, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------ engine API
 int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (!cfg || !out) return MB_ERR_ARG;
@@ -441,6 +449,7 @@ void mb_bert_destroy(mb_bert_engine* e) {
     e->destroy_prof();
     e->drop_graphs();
     e->free_class_table();
+    e->free_clip_buf();
     delete e;
 }
 int mb_bert_num_tensors(const mb_bert_engine* e) { return (int)e->tensors.size(); }
@@ -848,13 +857,15 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
     const int se = nseg == 1 ? NL + 2 : (seg + 1 < nseg ? 1 + (seg + 1) * C : NL + 2);
     // (experiment) the layers' weights are updated by their own weight-gradient launches: single segment, known-zero gradients,
     // in-line 128 x 128 grouped launches, the layers' GEMM weights at the head of the decay slab
+    // (gradient-norm clipping, StepMixin::clip_step: no parameter may move before the whole gradient exists -- neither this nor riders)
+    const bool clip = e->clip_step && m && v;
     const bool fuse = e->adam_in_wgrad && m && v && nseg == 1 && e->ow_pass && e->grouped && e->group_wgrad == 128 && NL > 0 &&
-                      e->lo[0].wqkv == 0 && !e->prof && e->n_classes == 0;      // (one set of scalars: off in a classed step)
+                      e->lo[0].wqkv == 0 && !e->prof && e->n_classes == 0 && !clip;      // (one set of scalars: off in a classed step)
     e->fuse_m = fuse ? m : nullptr; e->fuse_v = fuse ? v : nullptr;
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside the weight-gradient launches of layers 0 .. NL-2; whether a launch
     // really carried one is decided there, so the sweep below asks the engine which layers are still to do
     const bool ride = e->ride_opts.ride && !fuse && m && v && nseg == 1 && e->grouped && NL > 1 && e->lo[0].wqkv == 0 && !e->prof &&
-                      (e->group_wgrad == 128 || e->group_wgrad == 256);
+                      (e->group_wgrad == 128 || e->group_wgrad == 256) && !clip;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wp;
     const int rb = mb_bert_backward(e, nullptr, lab, loss_scale, sb, se, st);
@@ -864,6 +875,10 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
     if (m && v && seg == nseg - 1) {
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_params;
+        if (clip) {          // the whole gradient is final: its norm, and the coefficient into the scalars the sweep below reads
+            if (nseg != 1) return MB_ERR_MODE;
+            CK(e->enqueue_clip(e->G, n, ws, st));
+        }
         CK(e->prof_mark(2 * NL, st));
         e->upd_ridden = ride ? e->wp - e->ride_cursor : 0; e->upd_swept = n - (fuse ? e->wp : e->upd_ridden);
         e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
@@ -948,6 +963,14 @@ int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept,
     if (!e) return MB_ERR_ARG;
     return e->update_stats(ridden, swept, segments);
 }
+int mb_bert_set_grad_clip(mb_bert_engine* e, float max_norm) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_grad_clip(max_norm);
+}
+int mb_bert_grad_clip_stats(mb_bert_engine* e, float* norm, float* coef, void* stream) {
+    if (!e) return MB_ERR_ARG;
+    return e->grad_clip_stats(norm, coef, (hipStream_t)stream);
+}
 
 int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                        const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
@@ -965,7 +988,7 @@ int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float*
     e->training = 1;
     CK(prepare_pass(e, T, st));
     int nseg = 1;
-    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof && e->n_classes == 0) {
+    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof && e->n_classes == 0 && !(e->clip_max > 0.f)) {
         nseg = c.num_layers / e->opt_chunk + 1;
         if (!e->opt_side) {
             CK((int)hipStreamCreateWithFlags(&e->opt_side, hipStreamNonBlocking));
@@ -1066,6 +1089,7 @@ int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const flo
                           float loss_scale, int mode, void* stream, mb_comm* comm) {
     hipStream_t st = (hipStream_t)stream;
     if (e && e->n_classes > 0) return MB_ERR_MODE;          // update classes: the single-process step only
+    if (e && e->clip_max > 0.f) return MB_ERR_MODE;         // gradient-norm clipping too (it would need the norm of the reduced gradient)
     if (!e || !e->P || !e->G || !e->ws || !comm) return MB_ERR_ARG;
     const mb_bert_config& c = e->c;
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;

@@ -218,6 +218,7 @@ struct StepGraph {
     const void* tag;                                // whose events the graphs' nodes record (the mb_comm of a data-parallel step), else null
     std::vector<hipGraph_t> graph; std::vector<hipGraphExec_t> exec;
     size_t ridden = 0, swept = 0; int segments = 0; // what the captured update covers (StepMixin::upd_*: a replay enqueues nothing on the host)
+    int clip = 0;                                   // the update clips the gradient norm (StepMixin::clip_max > 0; the value is device data)
     void destroy() {
         for (auto x : exec) if (x) hipGraphExecDestroy(x);
         for (auto g : graph) if (g) hipGraphDestroy(g);
@@ -435,6 +436,46 @@ struct StepMixin {
     }
     void free_class_table() { if (class_table) { hipFree(class_table); class_table = nullptr; } }
     AdamArgs* class_state(char*) const { return class_table; }
+    // Gradient-norm clipping (include/magbert_hip.h: mb_*_set_grad_clip; csrc/gradnorm.hip).  clip_max > 0: a step that ends with the
+    // optimizer runs without riders, and between its backward and its sweep the norm of G[0, n_update_end) is taken and the coefficient
+    // multiplied into the grad_scale of the tables the sweep reads (enqueue_clip).  clip_buf is device memory of the engine's own, like
+    // class_table: {norm, coef} of the last update, {max_norm, grad_scale} as the step prologue deposits them, then the per-block partials.
+    // On / off joins the identity of a captured graph (StepGraph::clip); the value never re-captures.
+    float clip_max = 0.f;
+    bool clip_step = false;        // the step being enqueued clips (set by train_step_impl: clip_max > 0 and m, v given)
+    bool clip_ran = false;         // an update with clipping was enqueued since it was turned on
+    char* clip_buf = nullptr; size_t clip_cap = 0;
+    float* clip_record() const { return (float*)clip_buf; }
+    float* clip_params() const { return (float*)clip_buf + 2; }
+    double* clip_partials() const { return (double*)(clip_buf + 256); }
+    int ensure_clip_buf(size_t n) {          // (never inside a capture: train_step_impl calls it before the prologue)
+        const size_t need = 256 + (size_t)grad_norm_blocks(n) * sizeof(double);
+        if (clip_buf && need > clip_cap) return MB_ERR_ARG;          // (n is the engine's update range: it never changes)
+        if (!clip_buf) { CK((int)hipMalloc((void**)&clip_buf, need)); clip_cap = need; }
+        return MB_OK;
+    }
+    void free_clip_buf() { if (clip_buf) { hipFree(clip_buf); clip_buf = nullptr; clip_cap = 0; } }
+    int set_grad_clip(float max_norm) {
+        const float v = (std::isfinite(max_norm) && max_norm > 0.f) ? max_norm : 0.f;
+        if ((v > 0.f) != (clip_max > 0.f)) clip_ran = false;
+        clip_max = v;
+        return MB_OK;
+    }
+    int grad_clip_stats(float* norm, float* coef, hipStream_t st) const {
+        if (!(clip_max > 0.f) || !clip_ran || !clip_buf) return MB_ERR_MODE;
+        float rec[2] = {0.f, 0.f};
+        CK((int)hipStreamSynchronize(st));
+        CK((int)hipMemcpy(rec, clip_record(), sizeof rec, hipMemcpyDeviceToHost));
+        if (norm) *norm = rec[0];
+        if (coef) *coef = rec[1];
+        return MB_OK;
+    }
+    // the two launches between the backward and the sweep of a clipping step: every gradient of G[0, n) is final
+    int enqueue_clip(const float* G, size_t n, char* ws, hipStream_t st) {
+        CK(grad_sumsq(G, n, clip_partials(), st));
+        ClipTables t = {{adam_state(ws), n_classes > 0 ? class_state(ws) : nullptr}, {2, n_classes}};
+        return grad_clip_finalize(clip_partials(), grad_norm_blocks(n), clip_params(), 0.f, 1.f, clip_record(), t, st);
+    }
     int set_update_map(const std::vector<TensorInfo>& tensors, size_t n_update_end, int nc, int ns, const size_t* bounds, const int* classes) {
         if (nc == 0) {          // back to the two parameter groups (graphs captured for them were never dropped)
             n_classes = 0; seg_bounds.clear(); seg_class.clear(); class_vals.clear();
@@ -538,6 +579,9 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (m && e->n_classes > 0 && variant == 0) variant = -e->map_version;
     e->upd_ridden = e->upd_swept = 0; e->upd_segments = 0;
     if (m && e->n_classes > 0) CK(e->ensure_class_table());
+    const bool clip = m && e->clip_max > 0.f;
+    if (clip && variant > 0) return MB_ERR_MODE;          // (the data-parallel steps refuse before they get here)
+    if (clip) CK(e->ensure_clip_buf(e->n_update_end()));
     // The step may be cut into `nseg` segments: enqueue_inner(seg, ...) issues the kernels of one (captured and replayed as its own
     // LINEAR graph), between(seg, st) runs on the host right after segment `seg` was enqueued and is never captured -- the place for
     // cross-stream events (a graph with a fork inside runs on ROCm 7.2's slow path; a chain of linear graphs does not).
@@ -550,6 +594,8 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
         E* e; bool ok, with_opt, stale_before;
         ~Flags() {
             e->in_step = false; e->loss_cleared = false; e->packed = false; e->packed_w = false; e->counted = false;
+            if (ok && e->clip_step) e->clip_ran = true;
+            e->clip_step = false;
             e->grads_zero = ok && with_opt;
             e->grads_stale = ok ? (with_opt && e->keep_in_step()) : stale_before;
             // an update was enqueued: its sweep left every word gradient zero, and the next batch is stamped with the next number
@@ -565,7 +611,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (!stamping) e->stamp_live = false;
     else if (e->word_zero) e->stamp_live = true;
     e->word_zero = false;                   // (this step's backward writes some of them)
-    e->in_step = true; e->ow_pass = ow != 0;
+    e->in_step = true; e->ow_pass = ow != 0; e->clip_step = clip;
     auto enqueue = [&](int sg, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
         return enqueue_inner(sg, lg, ls, lr_, m_, v_, sc, s);
     };
@@ -599,6 +645,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
             pa.cls[c] = k;
         }
         if (e->n_classes > 0) { pa.ncls = e->n_classes; pa.cls_dst = e->class_state(ws); }
+        if (clip) { pa.clip[0] = e->clip_max; pa.clip[1] = grad_scale; pa.clip_dst = e->clip_params(); }
     }
     CK(step_prologue(pa, st));
     if (mode == 2 || force_launches) {
@@ -615,13 +662,15 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     StepGraph* g = nullptr;
     for (auto& x : e->graphs)
         if (x.B == B && x.L == L && x.with_opt == (m != nullptr) && x.overwrite == ow && x.logits == logits && x.loss == loss && x.loss_run == loss_run &&
-            x.m == m && x.v == v && x.loss_scale == loss_scale && x.st == st && x.nseg == nseg && x.variant == variant && x.tag == tag) { g = &x; break; }
+            x.m == m && x.v == v && x.loss_scale == loss_scale && x.st == st && x.nseg == nseg && x.variant == variant && x.tag == tag &&
+            x.clip == (clip ? 1 : 0)) { g = &x; break; }
     if (!g) {
         if (e->graphs.size() >= 32) {          // callers that keep changing output pointers: do not grow without bound
             e->graphs.front().destroy();
             e->graphs.erase(e->graphs.begin());
         }
         StepGraph ng = {B, L, m != nullptr, ow, logits, loss, loss_run, m, v, loss_scale, st, nseg, variant, tag, {}, {}};
+        ng.clip = clip ? 1 : 0;
         hipStream_t cs = nullptr;
         CK(e->capture_stream(&cs));
         for (int sg = 0; sg < nseg; ++sg) {

@@ -321,6 +321,19 @@ struct AdamPieces { uint32_t begin4[MB_SWEEP_PIECES_MAX], start4[MB_SWEEP_PIECES
 int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
                         size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------ gradient-norm clipping (gradnorm.hip)
+// grad_sumsq: partial[b] = the sum over block b's share of g[0, n) of (double)g[i]^2, b < grad_norm_blocks(n) (<= 2048, a function of n
+// alone); g needs 4-byte alignment only.  No atomics, fixed order: the same bits on every run.
+// grad_clip_finalize (one block): sum = the partials in index order; norm = grad_scale * sqrt(sum); coef = min(1, max_norm / (norm + 1e-6))
+// in double (torch.nn.utils.clip_grad_norm_; a non-finite norm gives what the arithmetic gives); out2 = {(float)norm, (float)coef}; then
+// tab[k][0 .. count[k]).grad_scale *= (float)coef for both tables (a null table is skipped; 256 entries in all at most).  dyn (device
+// pointer, may be null): {max_norm, grad_scale} are read from there instead (replayed step graphs: PrologueArgs::clip).
+unsigned grad_norm_blocks(size_t n);
+int grad_sumsq(const float* g, size_t n, double* partial, hipStream_t st);
+struct ClipTables { AdamArgs* tab[2]; int count[2]; };
+int grad_clip_finalize(const double* partial, unsigned blocks, const float* dyn, float max_norm, float grad_scale, float* out2,
+                       const ClipTables& t, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------ step prologue (rowops.hip)
 // Everything that changes from one optimizer step to the next, moved into device memory by ONE small launch so that the rest
 // of the step can be a replayed hipGraph: the six batch tensors (gathered into the engine's fixed staging buffers), the
@@ -334,6 +347,7 @@ struct PrologueArgs {
     uint32_t* keys; int nsites;            // keys[2 * site + {0, 1}]
     AdamArgs adam[2]; AdamArgs* adam_dst;  // may be null
     AdamArgs cls[MB_CLASSES_MAX]; AdamArgs* cls_dst; int ncls;      // update classes of a classed step: cls_dst[0 .. ncls) = cls (cls_dst may be null)
+    float clip[2]; float* clip_dst;        // gradient-norm clipping: clip_dst[0 .. 1] = {max_norm, grad_scale} for grad_clip_finalize (may be null)
     uint32_t* zero_dw;                     // one dword cleared by the launch (the step's loss accumulator), may be null
     // modality tensors packed on the way in: src fp32 [rows][cols] (device or pinned host) -> dst [rows][pitch] of `dtype` (MAG's
     // GEMM operands; columns [cols, pitch) are never written and stay zero) -- what pack_pad does, without its two launches

@@ -781,6 +781,7 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
         }
         if (a.adam_dst && threadIdx.x < 2) a.adam_dst[threadIdx.x] = a.adam[threadIdx.x];
         if (a.cls_dst && (int)threadIdx.x < a.ncls) a.cls_dst[threadIdx.x] = a.cls[threadIdx.x];
+        if (a.clip_dst && threadIdx.x < 2) a.clip_dst[threadIdx.x] = a.clip[threadIdx.x];
     }
     if (tid == 0 && a.zero_dw) *a.zero_dw = 0u;
     // occurrences of every token id of this batch (a vocab-sized table that is all zero between steps): the embedding backward adds

@@ -28,6 +28,7 @@ struct mb_xlnet_engine : StepMixin {
     size_t word, wsum, bsum, wc, bc, mask_emb, small_decay_begin;
     size_t mag_whv, mag_wha, mag_wv, mag_wa, mag_bhv, mag_bha, mag_bv, mag_ba, mag_lnw, mag_lnb;
     size_t n_params, n_trainable, n_decay, sh_begin, sh_end;
+    size_t n_update_end() const { return n_trainable; }       // (StepMixin: the range an update covers, and its clipping norm)
     MagWs mw;
     size_t ws_mag, ws_magout, ws_pos, ws_xs, ws_head_z, ws_head_pooled;
     std::vector<size_t> ws_x;
@@ -252,6 +253,7 @@ void mb_xlnet_destroy(mb_xlnet_engine* e) {
     e->destroy_prof();
     e->drop_graphs();
     e->free_class_table();
+    e->free_clip_buf();
     delete e;
 }
 int mb_xlnet_num_tensors(const mb_xlnet_engine* e) { return (int)e->tensors.size(); }
@@ -613,13 +615,16 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
                         loss_run, st));
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside launches of the backward of layers 0 .. NL-2 (mb_xlnet_backward: take_ride);
     // whether a launch really carried one is decided there, so the sweep below asks the engine what is still to do
+    // (gradient-norm clipping, StepMixin::clip_step: no parameter may move before the whole gradient exists -- no riders)
+    const bool clip = e->clip_step && m && v;
     const bool ride = e->ride_opts.ride && m && v && e->c.dtype == DT_BF16 && e->group_wgrad > 0 && e->c.n_layer > 1 && e->lo[0].q == 0 &&
-                      !e->prof && !e->mems;
+                      !e->prof && !e->mems && !clip;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wsum;
     const int rb = mb_xlnet_backward(e, nullptr, lab, loss_scale, 0, e->c.n_layer + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
+    if (clip) CK(e->enqueue_clip(e->G, e->n_trainable, ws, st));      // the whole gradient is final: its norm, the coefficient into the sweep's scalars
     if (m && v) {
         e->upd_ridden = ride ? e->wsum - e->ride_cursor : 0; e->upd_swept = e->n_trainable - e->upd_ridden;
         e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
@@ -668,6 +673,14 @@ int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* l
 int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments) {
     if (!e) return MB_ERR_ARG;
     return e->update_stats(ridden, swept, segments);
+}
+int mb_xlnet_set_grad_clip(mb_xlnet_engine* e, float max_norm) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_grad_clip(max_norm);
+}
+int mb_xlnet_grad_clip_stats(mb_xlnet_engine* e, float* norm, float* coef, void* stream) {
+    if (!e) return MB_ERR_ARG;
+    return e->grad_clip_stats(norm, coef, (hipStream_t)stream);
 }
 
 int mb_xlnet_train_step(mb_xlnet_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
@@ -771,6 +784,7 @@ int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const f
                            float loss_scale, int mode, void* stream, mb_comm* comm) {
     hipStream_t st = (hipStream_t)stream;
     if (e && e->n_classes > 0) return MB_ERR_MODE;          // update classes: the single-process step only
+    if (e && e->clip_max > 0.f) return MB_ERR_MODE;         // gradient-norm clipping too
     if (!e || !e->P || !e->G || !e->ws || !comm) return MB_ERR_ARG;
     const mb_xlnet_config& c = e->c;
     if (B < 1 || B > c.max_batch || L < 1 || L > c.max_seq) return MB_ERR_SHAPE;

@@ -119,6 +119,9 @@ def get_parser():
     parser.add_argument("--head_learning_rate", type=float, default=None,
                         help="learning rate of the freshly initialised parameters (MAG, pooler, classifier / sequence summary, "
                              "logits projection); default: learning_rate")
+    parser.add_argument("--max_grad_norm", type=float, default=0.0,
+                        help="clip the global gradient norm to this value in front of every optimizer update, inside the single-call "
+                             "step (AdamW(max_grad_norm=...)); 0 = off, the default: the reference does not clip")
     return parser
 
 
@@ -420,7 +423,7 @@ def prep_for_training(num_train_optimization_steps: int):
                                      head_lr=args.head_learning_rate)
     else:
         groups = optimizer_grouped_parameters(model)
-    optimizer = AdamW(groups, lr=args.learning_rate)
+    optimizer = AdamW(groups, lr=args.learning_rate, max_grad_norm=args.max_grad_norm if args.max_grad_norm > 0 else None)
     scheduler = get_linear_schedule_with_warmup(
         optimizer, num_warmup_steps=args.warmup_proportion * num_train_optimization_steps,
         num_training_steps=num_train_optimization_steps)

@@ -8,7 +8,16 @@ Parameters that are views of a model's flat buffer (bert.py) are updated with ON
 contiguous flat range (m, v live in flat buffers too; the bf16 operand shadow is refreshed and the gradient cleared
 in the same pass); any other CUDA tensor gets one launch per tensor.  Formula: see oracle/optim_ref.py -- eps 1e-6
 outside the sqrt, bias correction folded into step_size, decoupled decay AFTER the update.
+
+AdamW(..., max_grad_norm=x) clips the global gradient norm as torch.nn.utils.clip_grad_norm_(parameters, x) would in front of
+step(), without scaling any gradient: one HIP pass reads the flat gradient range (csrc/gradnorm.hip), and the coefficient goes into the
+gradient scale of the update kernels.  Inside the single-call step (model.train_step) no host sync is involved; step() itself reads
+the coefficient back once.
 """
+import math
+import os
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -100,7 +109,7 @@ def layerwise_lr_groups(named_parameters, num_layers, lr, layer_decay=1.0, head_
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -110,11 +119,83 @@ class AdamW(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
         super().__init__(params, defaults)
         self.grad_scale = 1.0          # data parallel: 1/world_size when gradients were SUM-reduced
+        # global gradient-norm clipping (None, <= 0 or non-finite: off).  The norm is that of the gradient as the update sees it
+        # (grad_scale included) over every parameter of this optimizer; may be changed between steps.
+        self.max_grad_norm = max_grad_norm
+        self._clip_last = None         # where the last update left (norm, coef): a core (single-call step) or the two floats
         self.fused_zero_grad = True    # clear gradients inside the update kernel (zero_grad() then costs nothing)
         self._plan = None
         self._class_maps = {}          # per flat buffer: the segment map of a classed single-call step (flat_step_args), or None
         self._t = 0
         self._dp = None              # set by distributed.DataParallel
+
+    def _clip_value(self):
+        """max_grad_norm as the engine takes it: a float > 0, or 0.0 for off"""
+        x = self.max_grad_norm
+        if x is None:
+            return 0.0
+        x = float(x)
+        return x if (math.isfinite(x) and x > 0.0) else 0.0
+
+    @property
+    def last_grad_norm(self):
+        """the gradient norm the last clipped update measured (before clipping), None when no such update has run.  Read from the
+        device when asked for, not on every step."""
+        rec = self.last_grad_clip
+        return None if rec is None else rec[0]
+
+    @property
+    def last_grad_clip(self):
+        """(norm, coef) of the last clipped update, or None"""
+        if self._clip_last is None:
+            return None
+        if isinstance(self._clip_last, tuple):
+            return self._clip_last
+        return self._clip_last.grad_clip_stats()
+
+    def _clip_coef(self, L):
+        """step() with max_grad_norm: (norm, coef) over everything this optimizer is about to update.  The usual case -- one
+        contiguous flat range of one model, no loose tensor with a gradient -- is ONE mb_grad_clip_coef call whose coefficient is the
+        float the single-call step forms on the device.  Otherwise the pieces' norms (one call per contiguous flat range; loose
+        tensors with torch, in double) are combined on the host."""
+        max_norm = self._clip_value()
+        ranges = {}
+        for it in self._plan:
+            if it[0] == "flat":
+                ranges.setdefault(id(it[2]), (it[2], []))[1].append((it[3], it[4]))
+        pieces = []
+        for core, sp in ranges.values():
+            sp.sort()
+            merged = []
+            for a, b in sp:
+                if merged and a <= merged[-1][1]:
+                    merged[-1][1] = max(merged[-1][1], b)
+                elif b > a:
+                    merged.append([a, b])
+            pieces += [(core, a, b) for a, b in merged]
+        loose = [it[2] for it in self._plan if it[0] != "flat" and it[2].grad is not None]
+
+        def call(core, a, b):
+            n = b - a
+            need = L.mb_grad_clip_scratch_bytes(n)
+            scratch = getattr(core, "_clip_scratch", None)
+            if scratch is None or scratch.numel() * 8 < need:
+                scratch = core._clip_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=core.grads.device)
+                core._clip_out = torch.empty(2, dtype=torch.float32, device=core.grads.device)
+            _lib.check(L.mb_grad_clip_coef(core.grads.data_ptr() + 4 * a, n, max_norm, self.grad_scale, scratch.data_ptr(),
+                                           core._clip_out.data_ptr(), core.stream()))
+            norm, coef = core._clip_out.cpu().tolist()          # the one host sync of this path
+            return norm, coef
+
+        if len(pieces) == 1 and not loose:
+            return call(*pieces[0])
+        total = 0.0
+        for piece in pieces:
+            total += call(*piece)[0] ** 2
+        for p in loose:
+            total += float(p.grad.detach().double().pow(2).sum()) * float(self.grad_scale) ** 2
+        norm = math.sqrt(total)
+        return norm, float(np.float32(min(1.0, max_norm / (norm + 1e-6))))
 
     # -- planning: map groups onto contiguous flat ranges ------------------------------------------------
     def _build_plan(self):
@@ -189,11 +270,15 @@ class AdamW(torch.optim.Optimizer):
         correction in both -- the scalars of that update.  For any other set of groups that covers the buffer's trainable range exactly
         once: the same dictionary with "map" = (boundaries, classes), the segment map (plan_update_segments), and "classes" = the
         per-class lists lr / beta1 / beta2 / eps / weight_decay / correct_bias of this step (include/magbert_hip.h:
-        mb_*_set_update_map / _set_update_values).  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
+        mb_*_set_update_map / _set_update_values).  Either dictionary carries "max_grad_norm" (0.0 = no clipping), which the step installs
+        with mb_*_set_grad_clip; under allow_dp a clipping optimizer gets None -- the data-parallel single call has no norm of the reduced
+        gradient, so that step is driven from Python.  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
         segments than the engine takes, fused_zero_grad off, data parallel -- whose step keeps its Python-driven exchange for classed
         optimizers, allow_dp or not): the caller then runs step() as usual.  Used by the whole-step graph (mb_bert_train_step), which
         applies the update itself."""
         if (self._dp is not None and not allow_dp) or not self.fused_zero_grad:
+            return None
+        if allow_dp and self._clip_value() > 0.0:
             return None
         if self._plan is None:
             self._build_plan()
@@ -203,6 +288,8 @@ class AdamW(torch.optim.Optimizer):
             return None
         two = self._two_group_args(core, flats)
         if two is not None or self._dp is not None or not flats or any(it[2] is not core for it in flats):
+            if two is not None:
+                two["max_grad_norm"] = self._clip_value()
             return two
         planned = self._class_map(core)
         if planned is None:
@@ -210,6 +297,7 @@ class AdamW(torch.optim.Optimizer):
         boundaries, classes, groups = planned
         gs = [self.param_groups[g] for g in groups]
         return dict(m=core._adam_m, v=core._adam_v, grad_scale=float(self.grad_scale), map=(boundaries, classes),
+                    max_grad_norm=self._clip_value(),
                     classes=dict(lr=[float(g["lr"]) for g in gs], beta1=[float(g["betas"][0]) for g in gs],
                                  beta2=[float(g["betas"][1]) for g in gs], eps=[float(g["eps"]) for g in gs],
                                  weight_decay=[float(g["weight_decay"]) for g in gs],
@@ -247,6 +335,18 @@ class AdamW(torch.optim.Optimizer):
             late = sorted(dp.late_ranges)
 
         shards = getattr(dp, "shards", None) if dp is not None else None
+        grad_scale = self.grad_scale
+        if self._clip_value() > 0.0:
+            if shards is not None or getattr(dp, "shard_in_engine", False) or (dp is not None and os.environ.get("MB_DP_SHARD_OPT", "0") == "1"):
+                raise _lib.MagbertError("max_grad_norm with MB_DP_SHARD_OPT=1: a rank holds only its shard of the reduced gradient, "
+                                        "the norm would need a cross-rank sum -- not supported")
+            if dp is not None:
+                dp.finish()                # the norm needs the WHOLE reduced gradient: no late ranges in such a step
+                late = []
+            norm, coef = self._clip_coef(L)
+            # the product as ONE fp32 multiply: the float the device forms in the single-call step
+            grad_scale = float(np.float32(self.grad_scale) * np.float32(coef))
+            self._clip_last = (norm, coef)
 
         def launch(core, group, x, y):
             if shards is not None and core is shards.core and x < shards.hi and y > shards.lo:
@@ -270,7 +370,7 @@ class AdamW(torch.optim.Optimizer):
                 core.params.data_ptr() + 4 * x, core.grads.data_ptr() + 4 * x, core._adam_m.data_ptr() + 4 * x,
                 core._adam_v.data_ptr() + 4 * x, (sh.data_ptr() + 2 * x) if sh is not None else None, y - x,
                 (y - x) if group["weight_decay"] > 0.0 else 0, sb, se, group["lr"], b1, b2, group["eps"],
-                group["weight_decay"], self._t, 1 if group["correct_bias"] else 0, self.grad_scale,
+                group["weight_decay"], self._t, 1 if group["correct_bias"] else 0, grad_scale,
                 1 if self.fused_zero_grad else 0, core.stream()))
 
         deferred = []                      # (core, group, x, y) pieces that must wait for the last all-reduce
@@ -303,7 +403,7 @@ class AdamW(torch.optim.Optimizer):
                 _lib.check(L.mb_adamw_step(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(),
                                            state["exp_avg_sq"].data_ptr(), None, n, n if group["weight_decay"] > 0.0 else 0,
                                            0, 0, group["lr"], b1, b2, group["eps"], group["weight_decay"], self._t,
-                                           1 if group["correct_bias"] else 0, self.grad_scale, 0,
+                                           1 if group["correct_bias"] else 0, grad_scale, 0,
                                            torch.cuda.current_stream(p.device).cuda_stream))
         if late:
             dp.finish()                    # this stream now waits for the last all-reduce

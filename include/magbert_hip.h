@@ -139,6 +139,16 @@ int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n
                   size_t sh_end, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   int correct_bias, float grad_scale, int zero_grad, void* stream);
 
+/* Global gradient-norm clipping over a flat fp32 range (torch.nn.utils.clip_grad_norm_, error_if_nonfinite = False), without touching
+ * the gradients: out2 (device, two floats) = {norm, coef}, norm = grad_scale * sqrt(sum of g[i]^2) -- the norm of the gradient as
+ * mb_adamw_step(..., grad_scale, ...) sees it -- and coef = min(1, max_norm / (norm + 1e-6)); the caller passes grad_scale * coef as
+ * the grad_scale of its mb_adamw_step calls.  Every element is widened to double before it is squared and every sum is a double in
+ * a fixed order (no atomics): the same bits on every run, squares that would overflow or underflow fp32 included.  g needs 4-byte
+ * alignment only, any n.  scratch: caller-owned device memory of mb_grad_clip_scratch_bytes(n) bytes, 8-byte aligned; nothing is
+ * assumed about its contents.  Non-finite gradients give what the arithmetic gives (a NaN element: NaN norm and coefficient). */
+size_t mb_grad_clip_scratch_bytes(size_t n);
+int mb_grad_clip_coef(const float* g, size_t n, float max_norm, float grad_scale, void* scratch, float* out2, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ MAG-BERT engine
  * The whole MAG_BertForSequenceClassification forward / backward (bert.py:240-324 -> :76-237 -> modeling.py) as a
  * native step executor: one call enqueues every kernel of the pass on the stream (no Python between launches).   */
@@ -309,6 +319,20 @@ int mb_bert_set_update_map(mb_bert_engine* e, int n_classes, int n_segments, con
 int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                               const float* weight_decay, const int* correct_bias);
 int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments);
+
+/* Gradient-norm clipping inside mb_bert_train_step.  set_grad_clip: max_norm > 0 turns it on for every later step that ends with the
+ * optimizer (m, v given); max_norm <= 0 or non-finite turns it off, the default.  Sticky, like set_update_values.  Such a step updates
+ * no parameter before the whole gradient exists -- no riders in the backward launches, MB_ADAMW_IN_WGRAD and MB_ADAMW_OVERLAP off, so
+ * update_stats reports ridden == 0 -- and between its backward and its sweep takes the norm of the flat gradient range [0,
+ * mb_bert_param_count) as mb_grad_clip_coef does, with the step's grad_scale, and multiplies the coefficient into the gradient scale the
+ * sweep reads from device memory: one extra read of the gradient buffer, no pass that scales it.  After gradient-accumulation
+ * micro-steps (no m, v: unaffected) the clipped quantity is the accumulated gradient.  On / off is part of a captured graph's identity;
+ * the value reaches the device with the step prologue and never re-captures.  The scratch is device memory the engine allocates on
+ * the first such step: mb_bert_workspace_bytes does not change.  mb_bert_train_step_dp returns MB_ERR_MODE while clipping is on.
+ * grad_clip_stats: waits for `stream` and returns {norm, coef} of the last update; MB_ERR_MODE when clipping is off or no update has
+ * run since it was turned on.  Either pointer may be NULL. */
+int mb_bert_set_grad_clip(mb_bert_engine* e, float max_norm);
+int mb_bert_grad_clip_stats(mb_bert_engine* e, float* norm, float* coef, void* stream);
 
 /* Measurement hooks (bench.py): with profiling on, every per-layer grouped weight-gradient launch of mb_bert_backward is
  * bracketed by HIP timing events on the engine's internal side stream -- the stream that kernel runs on, which the
@@ -483,6 +507,10 @@ int mb_xlnet_set_update_map(mb_xlnet_engine* e, int n_classes, int n_segments, c
 int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                                const float* weight_decay, const int* correct_bias);
 int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments);
+/* gradient-norm clipping inside mb_xlnet_train_step: as mb_bert_set_grad_clip / _grad_clip_stats above; the norm covers
+ * [0, mb_xlnet_trainable_count) */
+int mb_xlnet_set_grad_clip(mb_xlnet_engine* e, float max_norm);
+int mb_xlnet_grad_clip_stats(mb_xlnet_engine* e, float* norm, float* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ data parallel (new)
  * The reference is single-device (global_configs.py:4,7; multimodal_driver.py:21 imports a DistributedSampler it never uses).

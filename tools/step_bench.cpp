@@ -15,6 +15,8 @@
 //   --layer_decay D, --head_lr_mult K (each off at 1; --graph 1|2, no --dp): per-group learning rates as update classes
 //            (mb_*_set_update_map / _set_update_values) -- layer l of N at lr * D^(N - l), the embeddings at lr * D^(N + 1), MAG / pooler /
 //            heads at K * lr, every learning rate split by the no-decay rule while that fits the class table (one class per depth otherwise)
+//   --max_grad_norm X (--graph 1|2, no --dp; 0 = off): gradient-norm clipping inside the step (mb_*_set_grad_clip); the norm and coefficient
+//            of the last update are printed
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
 // Prints one line per run: ms/step (HIP events around the K timed steps), host enqueue ms/step, samples/s, final loss.
@@ -42,7 +44,7 @@ struct Batch { int64_t *ids, *seg, *mask; float *vis, *aco, *lab; };
 int main(int argc, char** argv) {
     int steps = 30, warmup = 5, B = 48, L = 50, V = 47, A = 74, layers = 12, graph = 0, h2d = 0, nbatch = 4, dtype = MB_DT_BF16;
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
-    double layer_decay = 1.0, head_lr_mult = 1.0;
+    double layer_decay = 1.0, head_lr_mult = 1.0, max_grad_norm = 0.0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -54,9 +56,10 @@ int main(int argc, char** argv) {
         else if (k == "--hidden") hidden = atoi(v); else if (k == "--heads") heads = atoi(v); else if (k == "--inter") inter = atoi(v);
         else if (k == "--model") xl = strcmp(v, "xlnet") == 0;       // MAG-XLNet (BASELINE.json configs[3]): the single-call step only (--graph 1|2)
         else if (k == "--layer_decay") layer_decay = atof(v); else if (k == "--head_lr_mult") head_lr_mult = atof(v);
+        else if (k == "--max_grad_norm") max_grad_norm = atof(v);
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -187,6 +190,10 @@ int main(int argc, char** argv) {
         else { MCK(mb_bert_set_update_map(e, n_classes, n_segments, bounds.data(), cls.data()));
                MCK(mb_bert_set_update_values(e, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
     }
+    if (max_grad_norm > 0.0) {
+        if (!graph || dp) { fprintf(stderr, "--max_grad_norm: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
+        if (xl) MCK(mb_xlnet_set_grad_clip(ex, (float)max_grad_norm)); else MCK(mb_bert_set_grad_clip(e, (float)max_grad_norm));
+    }
     auto step = [&](int i) {
         char* src = db[i % nbatch];
         if (h2d == 1) HCK(hipMemcpyAsync(src, hb[i % nbatch], bytes, hipMemcpyHostToDevice, st));     // copy engine, same stream
@@ -238,6 +245,11 @@ int main(int argc, char** argv) {
         if (xl) MCK(mb_xlnet_update_stats(ex, &ridden, &swept, &segs)); else MCK(mb_bert_update_stats(e, &ridden, &swept, &segs));
         printf("step_bench update: classes=%d segments=%d ridden=%zu swept=%zu (layer_decay=%g head_lr_mult=%g)\n", n_classes, segs, ridden, swept,
                layer_decay, head_lr_mult);
+        if (max_grad_norm > 0.0) {
+            float norm = 0.f, coef = 0.f;
+            if (xl) MCK(mb_xlnet_grad_clip_stats(ex, &norm, &coef, st)); else MCK(mb_bert_grad_clip_stats(e, &norm, &coef, st));
+            printf("step_bench clip: max_grad_norm=%g last norm=%.6g coef=%.6g\n", max_grad_norm, norm, coef);
+        }
     }
     if (comm) {
         float ex = 0.f; size_t pieces = 0, cbytes = 0;
