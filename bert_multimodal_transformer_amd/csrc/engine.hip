@@ -13,8 +13,7 @@
 //                   classifier.weight
 //   no-decay group: per layer {q,k,v bias (contiguous [3H]), attn.out bias, LN1 w/b, inter bias, out bias, LN2 w/b};
 //                   embeddings.LayerNorm ; pooler bias ; MAG biases + LayerNorm ; classifier.bias
-#include "engine_common.h"
-#include "comm.h"
+#include "dp_step.h"
 
 // ================================================================================================ engine
 struct LayerOff { size_t wqkv, wo, w1, w2, bqkv, bo, ln1w, ln1b, b1, b2, ln2w, ln2b; };
@@ -28,6 +27,11 @@ struct mb_bert_engine : StepMixin {
     size_t mag_whv, mag_wha, mag_wv, mag_wa, mag_bhv, mag_bha, mag_bv, mag_ba, mag_lnw, mag_lnb;
     size_t n_params, n_decay, sh_begin, sh_end;
     size_t n_update_end() const { return n_params; }          // (StepMixin: the range an update covers, and its clipping norm)
+    // (dp_step.h: the layers' GEMM weights are [layer_begin(0), layers_end()) of the decay slab, layer by layer)
+    int n_layers() const { return c.num_layers; }
+    size_t layer_begin(int l) const { return lo[l].wqkv; }
+    size_t layers_end() const { return wp; }
+    int width() const { return c.hidden_size; }
     // workspace
     MagWs mw;
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
@@ -46,18 +50,10 @@ struct mb_bert_engine : StepMixin {
     const int64_t* ids = nullptr; const int64_t* seg = nullptr; const int64_t* mask = nullptr;
     int B = 0, L = 0, training = 0;
     int padT = -1;                 // token count whose pad rows [T, Tp) are currently known to be zero
-    // MB_ADAMW_OVERLAP=C: the single-call step forks the optimizer of every finished chunk of C layers onto this stream (enqueue_step)
-    int opt_chunk = 0;
     int prefetch = 1;              // MB_PREFETCH=0: the LayerNorm kernels do not touch the next GEMMs' weights (common.h Prefetch).  Touching
                                    // ACTIVATIONS the same way (GELU output for the weight gradient, saved q | k | v for the attention backward)
                                    // was measured +9 / +15 us per step and is not in the code (profiles/r03_prefetch_ab2.txt)
     int pf_qkv = 0;                // MB_PF_QKV=64|128: ln_bwd(LN1)'s left-over prefetch loads touch the saved q | k | v | context rows, one per 64 / 128 bytes
-    hipStream_t opt_side = nullptr;
-    std::vector<hipEvent_t> opt_ev;
-    // EXPERIMENT MB_ADAMW_IN_WGRAD=1 (kernels.h: EPI_WGRAD_ADAM): in a single-process single-call step whose gradient buffer is known-zero,
-    // the layers' grouped weight-gradient launches update the parameters themselves and the optimizer sweep skips that range.
-    int adam_in_wgrad = 0;
-    float* fuse_m = nullptr; float* fuse_v = nullptr;      // Adam moments of the step being enqueued, when the fusion applies to it
     // MB_ADAMW_RIDE=1 (kernels.h AdamRide): in a single-process single-call step the grouped weight-gradient launch of layer l carries
     // the optimizer update of layer l+1's GEMM weights (whose gradients the launch before completed) as extra workgroups in the slots
     // its tiles leave empty (256 x 128 tiles: 40 of 256 CUs; 128 x 128: 80 of 512 slots); the sweep at the end skips those layers.
@@ -423,13 +419,10 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     e->read_env();
     e->ride_opts.read_env();
     e->group_wgrad = env_int("MB_GROUP_WGRAD", e->group_wgrad);
-    e->adam_in_wgrad = env_int("MB_ADAMW_IN_WGRAD", e->adam_in_wgrad);
     e->ride_blocks = env_int("MB_ADAMW_RIDE_BLOCKS", e->ride_blocks);
     e->ride_params = env_long("MB_ADAMW_RIDE_PARAMS", e->ride_params);
-    e->opt_chunk = env_int("MB_ADAMW_OVERLAP", e->opt_chunk);
     e->prefetch = env_int("MB_PREFETCH", e->prefetch);
     e->pf_qkv = env_int("MB_PF_QKV", e->pf_qkv);
-    if (e->adam_in_wgrad && !getenv("MB_GROUP_WGRAD")) e->group_wgrad = 128;      // (that experiment lives in the 128 x 128 kernel's epilogue)
     // 256 = the 256 x 128 ping-pong tile (gemm_pp.hip; bf16 only): falls back to 128 where it does not divide the layer
     if (e->group_wgrad == 256 && (cfg->dtype != DT_BF16 || cfg->hidden_size % 256 != 0 || cfg->intermediate_size % 256 != 0)) e->group_wgrad = 128;
     e->grouped = (e->group_wgrad == 64 || e->group_wgrad == 128 || e->group_wgrad == 256) && cfg->hidden_size % e->group_wgrad == 0 &&
@@ -444,8 +437,6 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
 }
 void mb_bert_destroy(mb_bert_engine* e) {
     if (!e) return;
-    if (e->opt_side) hipStreamDestroy(e->opt_side);
-    for (auto& ev : e->opt_ev) if (ev) hipEventDestroy(ev);
     e->destroy_prof();
     e->drop_graphs();
     e->free_class_table();
@@ -727,22 +718,9 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                   e->key(SITE_LAYER0 + 4 * l + 0, c.attn_dropout), st,
                                   e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, ra.blocks ? &ra : nullptr,
                                   e->attn_stats(w)));
-            // (experiment) the update inside the launch: the tile of the gradient becomes the new parameters -- so every reader of the
-            // OLD weights of this layer (the qkv dgrad below) goes first
-            const bool fuse = grouped && e->fuse_m && e->fuse_v && e->ow_pass && e->group_wgrad == 128;
-            if (fuse) {
-                const size_t offs[4] = {o.w2, o.w1, o.wo, o.wqkv};
-                for (int k = 0; k < 4; ++k) {
-                    wg[k].C = P + offs[k]; wg[k].C2 = e->fuse_m + offs[k]; wg[k].R = e->fuse_v + offs[k];
-                    wg[k].bias = (const float*)e->adam_state(ws);
-                    wg[k].colsum = dt == DT_BF16 ? (float*)(e->SH + offs[k] * 2) : nullptr;
-                }
-                CK(gemm(dt, GEMM_NN, EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, nullptr, nullptr,
-                        nullptr, dsB, H, kNoDrop, 1, 0, st));
-            }
             // riders: an optimizer update in the empty slots of this launch (take_ride, below the loop header)
             AdamRide ride = {};
-            if (grouped && !fuse) {
+            if (grouped) {
                 int tiles = 0;
                 const int bm = wtile == 256 ? 256 : wtile, bn = wtile == 256 ? 128 : wtile;
                 for (const GemmArgs& a : wg) tiles += (a.M / bm) * (a.N / bn);
@@ -754,12 +732,12 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             }
             if (grouped) {
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], st));
-                CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, fuse, ride.blocks ? &ride : nullptr));
+                CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, ride.blocks ? &ride : nullptr));
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], st));
             } else {
                 CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, st));
             }
-            if (!fuse) CK(dgrad_ride(EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, dsB, H, nullptr));
+            CK(dgrad_ride(EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, dsB, H, nullptr));
         } else {
             // ---- MAG + embeddings
             char* dx = ws + e->ws_dxa;
@@ -821,24 +799,8 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
 // reference for the graph; also what runs while profiling events are on).  The prologue also converts the modality tensors into
 // MAG's packed GEMM operands, counts the occurrences of every token id and clears the loss accumulator (rowops.hip).
 
-// AdamW of flat range [b, en) of the decay slab (GEMM weights), inside a step (scalars from device memory)
-static int adamw_decay_range(mb_bert_engine* e, float* m, float* v, size_t b, size_t en, hipStream_t st) {
-    if (en <= b) return MB_OK;
-    const AdamArgs none = {};
-    const bool keep = e->keep_in_step();          // the layers' GEMM weight gradients: overwritten by the next backward, not zeroed
-    auto clampr = [&](size_t x) { return x < b ? (size_t)0 : (x > en ? en - b : x - b); };
-    const size_t shb = clampr(e->sh_begin), she = clampr(e->sh_end);
-    const size_t kb = keep ? clampr(e->stale_begin) : 0, ke = keep ? clampr(e->stale_end) : 0;
-    void* sh = e->c.dtype == DT_BF16 ? (void*)(e->SH + b * 2) : nullptr;
-    return adamw_step(e->P + b, e->G + b, m + b, v + b, sh, en - b, en - b, shb, she, none, 1, st, e->adam_state(e->ws), kb, ke);
-}
-
-// The step as `nseg` segments (train_step_impl).  nseg == 1: forward, backward, optimizer.  MB_ADAMW_OVERLAP=C (C layers per chunk,
-// nseg = layers / C + 1): segment i ends with the backward of a chunk of C layers; the host then forks the AdamW of THAT chunk's
-// GEMM weights (7.08 M parameters per layer, 77 % of the model: HBM-bound) onto the optimizer side stream, where it runs under the
-// MFMA-bound backward of the layers below; the last segment holds the MAG / embedding backward and the optimizer of everything
-// else, and the step ends with the join.  Nothing later in the step reads a finished layer's weights, gradients or shadow.
-static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, float* logits, float* loss, float* loss_run, float* m, float* v,
+// The kernels of the step: forward, backward, optimizer (adamw_decay_range: dp_step.h)
+static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* loss, float* loss_run, float* m, float* v,
                         float loss_scale, hipStream_t st) {
     char* ws = e->ws;
     const int NL = e->c.num_layers;
@@ -847,45 +809,31 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
     e->attn_out = nullptr;                      // optional outputs belong to explicit forwards, never to a (captured) training step
     struct Restore { mb_bert_engine* e; float* p; ~Restore() { e->attn_out = p; } } restore{e, keep_attn};
     if (e->head_mask || e->emb_in || e->pos_ids) return MB_ERR_MODE;     // head_mask / inputs_embeds / position_ids are arguments of explicit forwards only
-    const int C = nseg > 1 ? NL / (nseg - 1) : 0;
-    if (seg == 0)
-        CK(mb_bert_forward(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
-                           (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, logits, loss,
-                           loss_run, st));
-    // backward stages: 0 = head, 1 .. NL = layers NL-1 .. 0, NL+1 = MAG + embeddings
-    const int sb = nseg == 1 ? 0 : (seg == 0 ? 0 : 1 + seg * C);
-    const int se = nseg == 1 ? NL + 2 : (seg + 1 < nseg ? 1 + (seg + 1) * C : NL + 2);
-    // (experiment) the layers' weights are updated by their own weight-gradient launches: single segment, known-zero gradients,
-    // in-line 128 x 128 grouped launches, the layers' GEMM weights at the head of the decay slab
-    // (gradient-norm clipping, StepMixin::clip_step: no parameter may move before the whole gradient exists -- neither this nor riders)
+    CK(mb_bert_forward(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
+                       (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, logits, loss,
+                       loss_run, st));
+    // (gradient-norm clipping, StepMixin::clip_step: no parameter may move before the whole gradient exists -- no riders)
     const bool clip = e->clip_step && m && v;
-    const bool fuse = e->adam_in_wgrad && m && v && nseg == 1 && e->ow_pass && e->grouped && e->group_wgrad == 128 && NL > 0 &&
-                      e->lo[0].wqkv == 0 && !e->prof && e->n_classes == 0 && !clip;      // (one set of scalars: off in a classed step)
-    e->fuse_m = fuse ? m : nullptr; e->fuse_v = fuse ? v : nullptr;
     // riders (MB_ADAMW_RIDE): layers 1 .. NL-1 are updated inside the weight-gradient launches of layers 0 .. NL-2; whether a launch
     // really carried one is decided there, so the sweep below asks the engine which layers are still to do
-    const bool ride = e->ride_opts.ride && !fuse && m && v && nseg == 1 && e->grouped && NL > 1 && e->lo[0].wqkv == 0 && !e->prof &&
+    const bool ride = e->ride_opts.ride && m && v && e->grouped && NL > 1 && e->lo[0].wqkv == 0 && !e->prof &&
                       (e->group_wgrad == 128 || e->group_wgrad == 256) && !clip;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wp;
-    const int rb = mb_bert_backward(e, nullptr, lab, loss_scale, sb, se, st);
-    e->fuse_m = e->fuse_v = nullptr;
+    // backward stages: 0 = head, 1 .. NL = layers NL-1 .. 0, NL+1 = MAG + embeddings
+    const int rb = mb_bert_backward(e, nullptr, lab, loss_scale, 0, NL + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
-    if (m && v && seg == nseg - 1) {
+    if (m && v) {
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_params;
-        if (clip) {          // the whole gradient is final: its norm, and the coefficient into the scalars the sweep below reads
-            if (nseg != 1) return MB_ERR_MODE;
-            CK(e->enqueue_clip(e->G, n, ws, st));
-        }
+        if (clip) CK(e->enqueue_clip(e->G, n, ws, st));      // the whole gradient is final: its norm, and the coefficient into the scalars the sweep below reads
         CK(e->prof_mark(2 * NL, st));
-        e->upd_ridden = ride ? e->wp - e->ride_cursor : 0; e->upd_swept = n - (fuse ? e->wp : e->upd_ridden);
+        e->upd_ridden = ride ? e->wp - e->ride_cursor : 0; e->upd_swept = n - e->upd_ridden;
         e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
         if (e->n_classes > 0) {
             // Classed step (kernels.h AdamPieces): the same ranges cut at the segment boundaries, every piece with its class's slot, ONE
             // launch; the word rows and the keep range as below
-            if (nseg != 1) return MB_ERR_MODE;
             AdamPieces pieces;
             CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wp, e->wp, n));
             const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
@@ -903,13 +851,13 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
         // batches did not touch alone when the engine can vouch for their zeros (WordSkip, StepMixin::stamp_live: the prologue put the
         // verdict of THIS step into device memory, so the captured launch is the same either way).  Both off: the three launches below.
         const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
-        if (nseg == 1 && (e->one_sweep || skip)) {
+        if (e->one_sweep || skip) {
             AdamRanges all = {};
             auto add = [&](size_t b, size_t en, int slot) {
                 if (en > b) { all.begin[all.count] = b; all.n[all.count] = en - b; all.slot[all.count] = slot; ++all.count; }
             };
             if (ride) add(0, e->ride_cursor, 0);
-            add((!fuse && !ride) ? 0 : e->wp, nd, 0);
+            add(ride ? e->wp : 0, nd, 0);
             add(nd, n, 1);
             const bool keep = e->keep_in_step();
             WordSkip ws_ = {};
@@ -925,27 +873,10 @@ static int enqueue_step(mb_bert_engine* e, int seg, int nseg, int B, int L, floa
             CK(e->prof_mark(2 * NL + 1, st));
             return MB_OK;
         }
-        // (with chunks on the side stream, what is left of the decay slab: the pooler weight .. the classifier weight)
         if (ride) CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));       // what no launch carried (layer 0 always)
-        CK(adamw_decay_range(e, m, v, (nseg == 1 && !fuse && !ride) ? 0 : e->wp, nd, st));
+        CK(adamw_decay_range(e, m, v, ride ? e->wp : 0, nd, st));
         CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
         CK(e->prof_mark(2 * NL + 1, st));
-    }
-    return MB_OK;
-}
-
-// host side of MB_ADAMW_OVERLAP, after segment `seg` was enqueued (never captured): fork the chunk's optimizer / join at the end
-static int between_segments(mb_bert_engine* e, int seg, int nseg, float* m, float* v, hipStream_t st) {
-    if (nseg == 1 || !m || !v) return MB_OK;
-    const int NL = e->c.num_layers, C = NL / (nseg - 1);
-    if (seg + 1 < nseg) {
-        const int l_lo = NL - (seg + 1) * C, l_hi = NL - seg * C;       // layers [l_lo, l_hi) finished in this segment
-        CK((int)hipEventRecord(e->opt_ev[seg], st));
-        CK((int)hipStreamWaitEvent(e->opt_side, e->opt_ev[seg], 0));
-        CK(adamw_decay_range(e, m, v, e->lo[l_lo].wqkv, l_hi < NL ? e->lo[l_hi].wqkv : e->wp, e->opt_side));
-    } else {
-        CK((int)hipEventRecord(e->opt_ev[seg], e->opt_side));
-        CK((int)hipStreamWaitEvent(st, e->opt_ev[seg], 0));
     }
     return MB_OK;
 }
@@ -987,101 +918,16 @@ int mb_bert_train_step(mb_bert_engine* e, const int64_t* input_ids, const float*
     char* ws = e->ws;
     e->training = 1;
     CK(prepare_pass(e, T, st));
-    int nseg = 1;
-    if (m && e->opt_chunk > 0 && c.num_layers % e->opt_chunk == 0 && !e->prof && e->n_classes == 0 && !(e->clip_max > 0.f)) {
-        nseg = c.num_layers / e->opt_chunk + 1;
-        if (!e->opt_side) {
-            CK((int)hipStreamCreateWithFlags(&e->opt_side, hipStreamNonBlocking));
-            e->opt_ev.assign((size_t)c.num_layers + 1, nullptr);
-            for (auto& ev : e->opt_ev) CK((int)hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-    }
     return train_step_impl(e, ws, c.visual_dim, c.acoustic_dim, c.num_labels, input_ids, visual, acoustic, attention_mask, token_type_ids,
                            labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2, eps, weight_decay, opt_step,
                            correct_bias, grad_scale, loss_scale, mode, e->prof, st,
-                           [&](int sg, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
-                               return enqueue_step(e, sg, nseg, B, L, lg, ls, lr_, m_, v_, sc, s);
-                           },
-                           nseg, [&](int sg, hipStream_t s) { return between_segments(e, sg, nseg, m, v, s); });
+                           [&](int, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
+                               return enqueue_step(e, B, L, lg, ls, lr_, m_, v_, sc, s);
+                           });
 }
 
 // ------------------------------------------------------------------------------------------------ data-parallel step, one call
-// mb_bert_train_step with the gradient exchange inside (include/magbert_hip.h, csrc/comm.hip).  `plan` = layers per backward segment
-// (dp_chunk_plan: 4, 4, 2, 2).  Segments, each a LINEAR graph:
-//   s < nb      : (s = 0: forward + head) + the backward of plan[s] layers (+ s = nb-1: MAG + embeddings + the ONE LayerNorm / bias
-//                 reduction)                 -> between: all-reduce of those layers' GEMM weights (the last one: + the tail's exchange)
-//   nb          : AdamW over the GEMM weights of every layer but the last segment's   (waits for the early pieces only)
-//   nb + 1      : AdamW over the last segment's layers, the rest of the decay slab and the no-decay slab   (waits for everything)
-// AdamW over [b, en) of the decay slab inside a data-parallel step.  Sharded update (comm->shard): of every chunk of layer GEMM weights
-// inside the range only this rank's slice and the replicated remainder are updated (csrc/comm.h: dp_shard_slice); the other slices'
-// gradient copies were not reduced here -- they are dead, and cleared unless the next backward overwrites them anyway.
-static int adamw_decay_range_dp(mb_bert_engine* e, const mb_comm* comm, const DpSpec& sp, float* m, float* v, size_t b, size_t en, hipStream_t st) {
-    if (!comm->shard) return adamw_decay_range(e, m, v, b, en, st);
-    std::vector<std::pair<size_t, size_t>> ch(sp.chunk.begin(), sp.chunk.begin() + sp.n_sharded);      // (the rest is replicated)
-    std::sort(ch.begin(), ch.end());
-    size_t cur = b;
-    ZeroRanges dead = {};
-    for (const auto& c : ch) {
-        if (c.second <= cur || c.first >= en) continue;
-        if (c.first < cur || c.second > en) return MB_ERR_MODE;          // (ranges are unions of whole chunks)
-        CK(adamw_decay_range(e, m, v, cur, c.first, st));
-        const ShardSlice sl = dp_shard_slice(comm, c.first, c.second);
-        CK(adamw_decay_range(e, m, v, sl.mine_b, sl.mine_e, st));
-        CK(adamw_decay_range(e, m, v, sl.rem_b, sl.rem_e, st));
-        if (!e->keep_in_step()) {
-            if (dead.n + 2 > MB_ZERO_MAX) { CK(zero_fill_ranges(dead, st)); dead = ZeroRanges{}; }       // (add() drops what does not fit)
-            dead.add(e->G + c.first, (sl.mine_b - c.first) * 4);
-            dead.add(e->G + sl.mine_e, (sl.rem_b - sl.mine_e) * 4);
-        }
-        cur = c.second;
-    }
-    if (dead.n) CK(zero_fill_ranges(dead, st));
-    return adamw_decay_range(e, m, v, cur, en, st);
-}
-
-static int enqueue_step_dp(mb_bert_engine* e, int seg, const std::vector<int>& plan, const mb_comm* comm, const DpSpec& sp, int B, int L,
-                           float* logits, float* loss, float* loss_run, float* m, float* v, float loss_scale, hipStream_t st) {
-    char* ws = e->ws;
-    const int NL = e->c.num_layers, nb = (int)plan.size();
-    const float* lab = (const float*)(ws + e->ws_in_lab);
-    float* keep_attn = e->attn_out;
-    e->attn_out = nullptr;
-    struct Restore { mb_bert_engine* e; float* p; ~Restore() { e->attn_out = p; } } restore{e, keep_attn};
-    if (e->head_mask || e->emb_in || e->pos_ids) return MB_ERR_MODE;
-    // sharded update with several pieces: nf forward-only segments in front (piece k = the layers of chunk nb-1-k, lowest first); the
-    // last piece -- the top layers + head -- stays in front of the first backward segment
-    const int nf = comm->nf;
-    auto layers_of = [&](int chunk, int& l0, int& l1) { l1 = NL; for (int s = 0; s < chunk; ++s) l1 -= plan[s]; l0 = l1 - plan[chunk]; };
-    if (seg <= nf) {
-        int l0 = 0, l1 = NL;
-        if (nf > 0) layers_of(nb - 1 - seg, l0, l1);
-        CK(bert_forward_range(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
-                              (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, logits, loss,
-                              loss_run, st, l0, l1, seg == 0, seg == nf));
-        if (seg < nf) return MB_OK;
-    }
-    seg -= nf;
-    if (seg < nb) {
-        int done = 0;
-        for (int s = 0; s < seg; ++s) done += plan[s];
-        // backward stages: 0 = head, 1 .. NL = layers NL-1 .. 0, NL+1 = MAG + embeddings
-        return mb_bert_backward(e, nullptr, lab, loss_scale, seg == 0 ? 0 : 1 + done, seg == nb - 1 ? NL + 2 : 1 + done + plan[seg], st);
-    }
-    const AdamArgs none = {};
-    const size_t nd = e->n_decay, n = e->n_params;
-    const size_t split = e->lo[plan[nb - 1] < NL ? plan[nb - 1] : 0].wqkv;      // first GEMM weight of the layers reduced early
-    if (seg == nb) {
-        CK(e->prof_mark(2 * NL, st));
-        if (nb > 1) return adamw_decay_range_dp(e, comm, sp, m, v, split, e->wp, st);
-        // (one backward segment: no early range -- dp_between waited for everything -- so this segment takes the no-decay slab)
-        return adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1);
-    }
-    CK(adamw_decay_range_dp(e, comm, sp, m, v, 0, nb > 1 ? split : e->wp, st));
-    CK(adamw_decay_range(e, m, v, e->wp, nd, st));
-    if (nb > 1) CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
-    return e->prof_mark(2 * NL + 1, st);
-}
-
+// mb_bert_train_step with the gradient exchange inside: the segments, their optimizer ranges and the step driver are dp_step.h's
 int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                           const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
                           uint64_t seed, uint64_t step, float* logits, float* loss, float* loss_run, float* m, float* v, float lr,
@@ -1096,46 +942,24 @@ int mb_bert_train_step_dp(mb_bert_engine* e, const int64_t* input_ids, const flo
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if (!m || !v || (mode != 1 && mode != 2)) return MB_ERR_ARG;
     if (!e->grouped) return MB_ERR_MODE;      // the exchange's pieces assume a layer's weight gradients are final when its stage returns
-    const int NL = c.num_layers;
-    const std::vector<int> plan = dp_chunk_plan(NL);
-    const int nb = (int)plan.size();
-    DpSpec sp;
-    for (int s = 0, hi = NL; s < nb; ++s) {            // segment s finishes layers [hi - plan[s], hi)
-        const int lo_l = hi - plan[s];
-        sp.chunk.push_back({e->lo[lo_l].wqkv, hi < NL ? e->lo[hi].wqkv : e->wp});
-        hi = lo_l;
-    }
-    sp.tail_begin = e->wp; sp.tail_end = e->n_params;
-    sp.word_off = e->word; sp.word_rows = c.vocab_size; sp.H = c.hidden_size;
-    sp.ids = (const int64_t*)(e->ws + e->ws_in_ids); sp.T = B * L;
-    sp.n_sharded = dp_sharded_chunks(comm, nb);
-    const int nf = dp_forward_segments(comm, nb);
-    comm->nf = nf;
-    if (comm->shard) {
-        // what the next forward reads of a layer's GEMM weights: their bf16 shadow (bf16 mode) or the fp32 parameters themselves
-        const bool bf = c.dtype == DT_BF16;
-        for (const auto& ch : sp.chunk)
-            if (bf && (!e->SH || ch.first < e->sh_begin || ch.second > e->sh_end)) return MB_ERR_MODE;
-        sp.gather_base = bf ? (char*)e->SH : (char*)e->P; sp.gather_es = bf ? 2 : 4;
-    }
-    CK(dp_step_begin(comm, st, nf > 0));          // (sharded update: the previous step's all-gathers -- cut mode: awaited piece by piece)
-    e->training = 1;
-    CK(prepare_pass(e, B * L, st));
-    // (the plan is part of the graphs' identity: nseg alone would not tell 4,4,2,2 from 2,2,4,4)
-    unsigned vh = 1;                                   // (unsigned: deep models have many pieces, the hash may wrap)
-    for (int x : plan) vh = vh * 13u + (unsigned)x;
-    vh = (vh * 4u + (unsigned)comm->event_mode) * 2u + (comm->shard ? 1u : 0u);
-    const int variant = (int)(vh & 0x7fffffffu) | 1;   // never 0, the single-process step's
-    return train_step_impl(e, e->ws, c.visual_dim, c.acoustic_dim, c.num_labels, input_ids, visual, acoustic, attention_mask, token_type_ids,
-                           labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2, eps, weight_decay, opt_step,
-                           correct_bias, grad_scale, loss_scale, mode, e->prof, st,
-                           [&](int sg, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
-                               CK(dp_segment_begin(comm, nb, sg, s));
-                               CK(enqueue_step_dp(e, sg, plan, comm, sp, B, L, lg, ls, lr_, m_, v_, sc, s));
-                               CK(dp_segment_end(comm, nb, sg, s));
-                               return (int)MB_OK;
-                           },
-                           nf + nb + 2, [&](int sg, hipStream_t s) { return dp_between(comm, sp, e->G, sg, s); }, variant, comm, dp_finish_segment_graph);
+    char* ws = e->ws;
+    const float* lab = (const float*)(ws + e->ws_in_lab);
+    return train_step_dp(
+        e, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2,
+        eps, weight_decay, opt_step, correct_bias, grad_scale, loss_scale, mode, st, comm,
+        [&](int T, hipStream_t s) { return prepare_pass(e, T, s); },
+        [&](int l0, int l1, bool first, bool last, float* lg, float* ls, float* lr_, hipStream_t s) {
+            float* keep_attn = e->attn_out;
+            e->attn_out = nullptr;                      // optional outputs belong to explicit forwards, never to a (captured) training step
+            struct Restore { mb_bert_engine* e; float* p; ~Restore() { e->attn_out = p; } } restore{e, keep_attn};
+            if (e->head_mask || e->emb_in || e->pos_ids) return (int)MB_ERR_MODE;
+            return bert_forward_range(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
+                                      (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, lg, ls, lr_, s,
+                                      l0, l1, first, last);
+        },
+        [&](int stage_begin, int stage_end, float loss_scale_, hipStream_t s) {
+            return mb_bert_backward(e, nullptr, lab, loss_scale_, stage_begin, stage_end, s);
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ stage-driven step (data parallel)

@@ -575,19 +575,11 @@ __device__ __forceinline__ void grouped_tn_block(const GroupedGemmArgs& ga) {
     }
     int g, m0, n0;
     if (!grouped_tile_origin<BM, BN>(ga, g, m0, n0)) return;
-    // (EPI_WGRAD_ADAM: touching the tile's p | m | v patch in front of the k loop -- one dword per 128-byte line, so that the epilogue
-    //  finds it in the L2 / Infinity Cache -- was measured and lost: 91 instead of 80 us per launch, profiles/r05_adamw_in_wgrad_ab.txt)
     gemm2_body<T, BM, BN, true, true, MODE, NSTAGE, KB>(ga.g[g], m0, n0, 0, smem);
 }
 template <class T, int BM, int BN, int NSTAGE, int KB>
 __global__ void __launch_bounds__(256) gemm2_grouped_tn_kernel(const GroupedGemmArgs ga) {
     grouped_tn_block<T, BM, BN, NSTAGE, KB, EPI_ACCUM_F32>(ga);
-}
-// (experiment, kernels.h EPI_WGRAD_ADAM: the same launch with HF-AdamW in the epilogue -- a kernel of its own so that the symbol of the
-//  default one, which profiles and PMC tables are keyed by, stays what it was)
-template <class T, int BM, int BN, int NSTAGE, int KB>
-__global__ void __launch_bounds__(256) gemm2_grouped_tn_adam_kernel(const GroupedGemmArgs ga) {
-    grouped_tn_block<T, BM, BN, NSTAGE, KB, EPI_WGRAD_ADAM>(ga);
 }
 
 // ---------------------------------------------------------------------------------------------- host
@@ -924,14 +916,14 @@ static int launch_T(const GemmArgs& a, int layout, int mode, int splits, int til
 }
 
 template <class T, int BM, int BN>
-static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int stages, bool adam, const AdamRide* ride) {
+static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int stages, const AdamRide* ride) {
     constexpr int BKE = 128 / sizeof(T);
     constexpr int EPV = 16 / sizeof(T);
     GroupedGemmArgs ga;
     ga.count = count;
     ga.ride = AdamRide{};
     if (ride && ride->blocks > 0 && ride->n4 > 0) {
-        if (ride->blocks % 8 || adam || BM < 128) return MB_ERR_ARG;
+        if (ride->blocks % 8 || BM < 128) return MB_ERR_ARG;
         ga.ride = *ride;
     }
     const HostEnv& env = host_env();
@@ -967,7 +959,6 @@ static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int 
         for (int i = 0; i < count; ++i) ga.g[i].trace = tr;
     }
     if constexpr (BM == 256) {          // 8-wave ping-pong tiles (gemm_pp.hip): one 256 x 128 tile per CU
-        if (adam) return MB_ERR_MODE;
         for (int i = 0; i < count; ++i) if (ga.g[i].K / BKE < 3) return MB_ERR_SHAPE;
         if (env.group_big == 2) return gemm_pp_grouped_launch(ga, grid, st);
         gemm_log_ride(ga.ride);
@@ -979,13 +970,6 @@ static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int 
     // A group of few 64 x 64 tiles (MAG: 360 tiles for 512 slots, 8 MFMAs per wave and stage) is pure load latency: one k stage
     // costs one memory round trip divided by the stages in flight.  4 | 5 ring slots of 128-byte rows = 64 | 80 KB, still 2 blocks
     // per CU.  (The 128 x 128 groups measured slower with any deeper ring: 128 KB would leave one block per CU.)
-    if (adam) {          // (experiment: the default 128 x 128 two-slot configuration only)
-        if constexpr (BM == 128 && BN == 128) {
-            MB_GEMM_LAUNCH((gemm2_grouped_tn_adam_kernel<T, BM, BN, 2, 128>), dim3(grid + ga.ride.blocks), dim3(256), st, ga, ga.g, count);
-            return (int)hipGetLastError();
-        }
-        return MB_ERR_MODE;
-    }
     if constexpr (BM == 64 && BN == 64) {
         if (gst == 4) { MB_GEMM_LAUNCH((gemm2_grouped_tn_kernel<T, BM, BN, 4, 128>), dim3(grid + ga.ride.blocks), dim3(256), st, ga, ga.g, count); return (int)hipGetLastError(); }
         if (gst == 5) { MB_GEMM_LAUNCH((gemm2_grouped_tn_kernel<T, BM, BN, 5, 128>), dim3(grid + ga.ride.blocks), dim3(256), st, ga, ga.g, count); return (int)hipGetLastError(); }
@@ -1019,11 +1003,11 @@ int gemm_grouped_tn_ok(int dtype, const GemmArgs* probs, int count, int tile) {
     return 1;
 }
 
-int gemm_grouped_tn_launch(int dtype, const GemmArgs* probs, int count, int tile, hipStream_t st, int stages, bool adam, const AdamRide* ride) {
+int gemm_grouped_tn_launch(int dtype, const GemmArgs* probs, int count, int tile, hipStream_t st, int stages, const AdamRide* ride) {
     if (count < 1 || count > MB_MAX_GROUP) return MB_ERR_ARG;
-    if (dtype == DT_BF16 && tile == 256) return launch_grouped<bf16, 256, 128>(probs, count, st, stages, adam, ride);
-    if (dtype == DT_BF16) return tile == 128 ? launch_grouped<bf16, 128, 128>(probs, count, st, stages, adam, ride) : launch_grouped<bf16, 64, 64>(probs, count, st, stages, adam, ride);
-    if (dtype == DT_F32) return tile == 128 ? launch_grouped<float, 128, 128>(probs, count, st, stages, adam, ride) : launch_grouped<float, 64, 64>(probs, count, st, stages, adam, ride);
+    if (dtype == DT_BF16 && tile == 256) return launch_grouped<bf16, 256, 128>(probs, count, st, stages, ride);
+    if (dtype == DT_BF16) return tile == 128 ? launch_grouped<bf16, 128, 128>(probs, count, st, stages, ride) : launch_grouped<bf16, 64, 64>(probs, count, st, stages, ride);
+    if (dtype == DT_F32) return tile == 128 ? launch_grouped<float, 128, 128>(probs, count, st, stages, ride) : launch_grouped<float, 64, 64>(probs, count, st, stages, ride);
     return MB_ERR_DTYPE;
 }
 

@@ -185,12 +185,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[KS
     const int c = (tid % TPR) * 8;
     const int n = n0 + c;
     float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    AdamArgs adam = {};
-    float adam_omb1 = 0.f, adam_omb2 = 0.f, adam_decay = 0.f;
-    if constexpr (MODE == EPI_WGRAD_ADAM) {
-        adam = *(const AdamArgs*)p.bias;          // this step's scalars (the step prologue wrote them)
-        adam_omb1 = 1.0f - adam.beta1; adam_omb2 = 1.0f - adam.beta2; adam_decay = adam.lr * adam.weight_decay;
-    }
     const float (&bias8)[8] = pre.bias8;
     T* __restrict__ C = (T*)p.C;
     const DropKey& dkey = pre.key;
@@ -264,23 +258,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[KS
 #pragma unroll
             for (int q = 0; q < 8; ++q) { v[q] *= res[q] * drop_mult(dkey, gidx + q); cs[q] += v[q]; }      // R = gelu'(u) saved by EPI_BIAS_GELU
             Vec8<T>::store(C + off, v);
-        } else if constexpr (MODE == EPI_WGRAD_ADAM) {
-            // the gradient never leaves the CU: HF-AdamW on this thread's eight parameters (adamw.hip: adam_update_store, same order of
-            // operations -> the same bits as storing the gradient and sweeping it later)
-            float* pp_ = (float*)p.C + off; float* pm_ = (float*)p.C2 + off; float* pv_ = (float*)const_cast<void*>(p.R) + off;
-            float pp[8], mm[8], vv[8];
-            Vec8<float>::load(pp_, pp); Vec8<float>::load(pm_, mm); Vec8<float>::load(pv_, vv);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-#pragma clang fp contract(off)
-                const float g = v[q] * adam.grad_scale;
-                mm[q] = adam.beta1 * mm[q] + adam_omb1 * g;
-                vv[q] = adam.beta2 * vv[q] + adam_omb2 * g * g;
-                pp[q] -= adam.step_size * (mm[q] / (sqrtf(vv[q]) + adam.eps));
-                if (adam_decay > 0.f) pp[q] -= adam_decay * pp[q];
-            }
-            Vec8<float>::store(pp_, pp); Vec8<float>::store(pm_, mm); Vec8<float>::store(pv_, vv);
-            if (p.colsum) Vec8<bf16>::store((bf16*)p.colsum + off, pp);
         } else if constexpr (MODE == EPI_ACCUM_F32) {
             float* dst = p.Cf + off;
             if (gridDim.y > 1) {

@@ -15,8 +15,7 @@
 //   no-decay : per layer r_r_bias, r_s_bias, r_w_bias, both layer_norm.bias, ff biases ; MAG biases + MAG.LayerNorm.* ;
 //              summary.bias ; logits_proj.bias
 //   frozen   : transformer.mask_emb (never receives a gradient in this configuration; HF AdamW skips grad-less parameters)
-#include "engine_common.h"
-#include "comm.h"
+#include "dp_step.h"
 
 struct XlLayerOff { size_t q, k, v, o, r, w1, w2, seg, ralnw, fflnw, rrb, rsb, rwb, ralnb, fflnb, b1, b2; };
 struct XlLayerWs { size_t qkv, kr, vec, psave, s1, st1, y1, u, g, s2, st2, stats; };     // max_seq > 128: stats (tiled attention's rows) instead of psave
@@ -29,6 +28,11 @@ struct mb_xlnet_engine : StepMixin {
     size_t mag_whv, mag_wha, mag_wv, mag_wa, mag_bhv, mag_bha, mag_bv, mag_ba, mag_lnw, mag_lnb;
     size_t n_params, n_trainable, n_decay, sh_begin, sh_end;
     size_t n_update_end() const { return n_trainable; }       // (StepMixin: the range an update covers, and its clipping norm)
+    // (dp_step.h: the layers' GEMM weights are [layer_begin(0), layers_end()) of the decay slab, layer by layer)
+    int n_layers() const { return c.n_layer; }
+    size_t layer_begin(int l) const { return lo[l].q; }
+    size_t layers_end() const { return wsum; }
+    int width() const { return c.d_model; }
     MagWs mw;
     size_t ws_mag, ws_magout, ws_pos, ws_xs, ws_head_z, ws_head_pooled;
     std::vector<size_t> ws_x;
@@ -605,7 +609,6 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
 }
 
 // ------------------------------------------------------------------------------------------------ whole step (as mb_bert_train_step)
-static int xl_adamw_decay_range(mb_xlnet_engine* e, float* m, float* v, size_t b, size_t en, hipStream_t st);
 static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, float* loss, float* loss_run, float* m, float* v,
                            float loss_scale, hipStream_t st) {
     char* ws = e->ws;
@@ -643,8 +646,8 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
         const AdamArgs none = {};
         const size_t nd = e->n_decay, n = e->n_trainable;
         CK(e->prof_mark(2 * e->c.n_layer, st));
-        CK(xl_adamw_decay_range(e, m, v, 0, e->ride_cursor, st));          // what no launch carried (layer 0 always)
-        CK(xl_adamw_decay_range(e, m, v, e->wsum, nd, st));
+        CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));          // what no launch carried (layer 0 always)
+        CK(adamw_decay_range(e, m, v, e->wsum, nd, st));
         CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
         CK(e->prof_mark(2 * e->c.n_layer + 1, st));
     } else if (m && v) {
@@ -705,78 +708,7 @@ int mb_xlnet_train_step(mb_xlnet_engine* e, const int64_t* input_ids, const floa
                            });
 }
 
-// ---- data-parallel step in one call (as mb_bert_train_step_dp: include/magbert_hip.h, csrc/comm.hip).  Segments: [0, nb) = (segment
-// 0: forward + head) + the backward of plan[s] layers (+ the last: the embedding stage) | nb = AdamW over the GEMM weights of the layers
-// reduced early | nb + 1 = AdamW over the last segment's layers and everything else
-static int xl_adamw_decay_range(mb_xlnet_engine* e, float* m, float* v, size_t b, size_t en, hipStream_t st) {
-    if (en <= b) return MB_OK;
-    const AdamArgs none = {};
-    const bool keep = e->keep_in_step();
-    auto clampr = [&](size_t x) { return x < b ? (size_t)0 : (x > en ? en - b : x - b); };
-    void* sh = e->c.dtype == DT_BF16 ? (void*)(e->SH + b * 2) : nullptr;
-    return adamw_step(e->P + b, e->G + b, m + b, v + b, sh, en - b, en - b, clampr(e->sh_begin), clampr(e->sh_end), none, 1, st,
-                      e->adam_state(e->ws), keep ? clampr(e->stale_begin) : 0, keep ? clampr(e->stale_end) : 0);
-}
-// sharded update: of every chunk of layer GEMM weights inside [b, en) only this rank's slice + the replicated remainder (engine.hip)
-static int xl_adamw_decay_range_dp(mb_xlnet_engine* e, const mb_comm* comm, const DpSpec& sp, float* m, float* v, size_t b, size_t en, hipStream_t st) {
-    if (!comm->shard) return xl_adamw_decay_range(e, m, v, b, en, st);
-    std::vector<std::pair<size_t, size_t>> ch(sp.chunk.begin(), sp.chunk.begin() + sp.n_sharded);      // (the rest is replicated)
-    std::sort(ch.begin(), ch.end());
-    size_t cur = b;
-    ZeroRanges dead = {};
-    for (const auto& c : ch) {
-        if (c.second <= cur || c.first >= en) continue;
-        if (c.first < cur || c.second > en) return MB_ERR_MODE;
-        CK(xl_adamw_decay_range(e, m, v, cur, c.first, st));
-        const ShardSlice sl = dp_shard_slice(comm, c.first, c.second);
-        CK(xl_adamw_decay_range(e, m, v, sl.mine_b, sl.mine_e, st));
-        CK(xl_adamw_decay_range(e, m, v, sl.rem_b, sl.rem_e, st));
-        if (!e->keep_in_step()) {
-            if (dead.n + 2 > MB_ZERO_MAX) { CK(zero_fill_ranges(dead, st)); dead = ZeroRanges{}; }       // (add() drops what does not fit)
-            dead.add(e->G + c.first, (sl.mine_b - c.first) * 4);
-            dead.add(e->G + sl.mine_e, (sl.rem_b - sl.mine_e) * 4);
-        }
-        cur = c.second;
-    }
-    if (dead.n) CK(zero_fill_ranges(dead, st));
-    return xl_adamw_decay_range(e, m, v, cur, en, st);
-}
-static int xl_enqueue_step_dp(mb_xlnet_engine* e, int seg, const std::vector<int>& plan, const mb_comm* comm, const DpSpec& sp, int B, int L,
-                              float* logits, float* loss, float* loss_run, float* m, float* v, float loss_scale, hipStream_t st) {
-    char* ws = e->ws;
-    const int NL = e->c.n_layer, nb = (int)plan.size();
-    const float* lab = (const float*)(ws + e->ws_in_lab);
-    const int nf = comm->nf;          // sharded update with several pieces: forward-only segments in front (engine.hip)
-    auto layers_of = [&](int chunk, int& l0, int& l1) { l1 = NL; for (int s = 0; s < chunk; ++s) l1 -= plan[s]; l0 = l1 - plan[chunk]; };
-    if (seg <= nf) {
-        int l0 = 0, l1 = NL;
-        if (nf > 0) layers_of(nb - 1 - seg, l0, l1);
-        CK(xl_forward_range(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
-                            (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, logits, loss,
-                            loss_run, st, l0, l1, seg == 0, seg == nf));
-        if (seg < nf) return MB_OK;
-    }
-    seg -= nf;
-    if (seg < nb) {
-        int done = 0;
-        for (int s = 0; s < seg; ++s) done += plan[s];
-        return mb_xlnet_backward(e, nullptr, lab, loss_scale, seg == 0 ? 0 : 1 + done, seg == nb - 1 ? NL + 2 : 1 + done + plan[seg], st);
-    }
-    const AdamArgs none = {};
-    const size_t nd = e->n_decay, n = e->n_trainable;
-    const size_t split = e->lo[plan[nb - 1] < NL ? plan[nb - 1] : 0].q;
-    if (seg == nb) {
-        CK(e->prof_mark(2 * NL, st));
-        if (nb > 1) return xl_adamw_decay_range_dp(e, comm, sp, m, v, split, e->wsum, st);
-        // (one backward segment: no early range -- dp_between waited for everything -- so this segment takes the no-decay slab)
-        return adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1);
-    }
-    CK(xl_adamw_decay_range_dp(e, comm, sp, m, v, 0, nb > 1 ? split : e->wsum, st));
-    CK(xl_adamw_decay_range(e, m, v, e->wsum, nd, st));
-    if (nb > 1) CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
-    return e->prof_mark(2 * NL + 1, st);
-}
-
+// ---- data-parallel step in one call: the segments, their optimizer ranges and the step driver are dp_step.h's
 int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                            const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
                            uint64_t seed, uint64_t step, float* logits, float* loss, float* loss_run, float* m, float* v, float lr,
@@ -791,44 +723,20 @@ int mb_xlnet_train_step_dp(mb_xlnet_engine* e, const int64_t* input_ids, const f
     if (!input_ids || !visual || !acoustic || !attention_mask || !token_type_ids || !labels || !logits || !loss) return MB_ERR_ARG;
     if (!m || !v || (mode != 1 && mode != 2)) return MB_ERR_ARG;
     if (e->head_mask || e->emb_in || e->perm || e->mems) return MB_ERR_MODE;
-    const int NL = c.n_layer;
-    const std::vector<int> plan = dp_chunk_plan(NL);
-    const int nb = (int)plan.size();
-    DpSpec sp;
-    for (int s = 0, hi = NL; s < nb; ++s) {
-        const int lo_l = hi - plan[s];
-        sp.chunk.push_back({e->lo[lo_l].q, hi < NL ? e->lo[hi].q : e->wsum});
-        hi = lo_l;
-    }
-    sp.tail_begin = e->wsum; sp.tail_end = e->n_trainable;
-    sp.word_off = e->word; sp.word_rows = c.vocab_size; sp.H = c.d_model;
-    sp.ids = (const int64_t*)(e->ws + e->ws_in_ids); sp.T = B * L;
-    sp.n_sharded = dp_sharded_chunks(comm, nb);
-    const int nf = dp_forward_segments(comm, nb);
-    comm->nf = nf;
-    if (comm->shard) {
-        const bool bf = c.dtype == DT_BF16;
-        for (const auto& ch : sp.chunk)
-            if (bf && (!e->SH || ch.first < e->sh_begin || ch.second > e->sh_end)) return MB_ERR_MODE;
-        sp.gather_base = bf ? (char*)e->SH : (char*)e->P; sp.gather_es = bf ? 2 : 4;
-    }
-    CK(dp_step_begin(comm, st, nf > 0));          // (sharded update: the previous step's all-gathers -- cut mode: awaited piece by piece)
-    e->training = 1;
-    CK(xl_prepare_pass(e, B * L, st));
-    unsigned vh = 1;                                   // (unsigned: deep models have many pieces, the hash may wrap -- as engine.hip)
-    for (int x : plan) vh = vh * 13u + (unsigned)x;
-    vh = (vh * 4u + (unsigned)comm->event_mode) * 2u + (comm->shard ? 1u : 0u);
-    const int variant = (int)(vh & 0x7fffffffu) | 1;   // never 0, the single-process step's
-    return train_step_impl(e, e->ws, c.visual_dim, c.acoustic_dim, c.num_labels, input_ids, visual, acoustic, attention_mask, token_type_ids,
-                           labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2, eps, weight_decay, opt_step,
-                           correct_bias, grad_scale, loss_scale, mode, e->prof, st,
-                           [&](int sg, float* lg, float* ls, float* lr_, float* m_, float* v_, float sc, hipStream_t s) {
-                               CK(dp_segment_begin(comm, nb, sg, s));
-                               CK(xl_enqueue_step_dp(e, sg, plan, comm, sp, B, L, lg, ls, lr_, m_, v_, sc, s));
-                               CK(dp_segment_end(comm, nb, sg, s));
-                               return (int)MB_OK;
-                           },
-                           nf + nb + 2, [&](int sg, hipStream_t s) { return dp_between(comm, sp, e->G, sg, s); }, variant, comm, dp_finish_segment_graph);
+    char* ws = e->ws;
+    const float* lab = (const float*)(ws + e->ws_in_lab);
+    return train_step_dp(
+        e, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, B, L, seed, step, logits, loss, loss_run, m, v, lr, beta1, beta2,
+        eps, weight_decay, opt_step, correct_bias, grad_scale, loss_scale, mode, st, comm,
+        [&](int T, hipStream_t s) { return xl_prepare_pass(e, T, s); },
+        [&](int l0, int l1, bool first, bool last, float* lg, float* ls, float* lr_, hipStream_t s) {
+            return xl_forward_range(e, (const int64_t*)(ws + e->ws_in_ids), (const float*)(ws + e->ws_in_vis), (const float*)(ws + e->ws_in_aco),
+                                    (const int64_t*)(ws + e->ws_in_mask), (const int64_t*)(ws + e->ws_in_seg), lab, B, L, 1, 0, 0, lg, ls, lr_, s,
+                                    l0, l1, first, last);
+        },
+        [&](int stage_begin, int stage_end, float loss_scale_, hipStream_t s) {
+            return mb_xlnet_backward(e, nullptr, lab, loss_scale_, stage_begin, stage_end, s);
+        });
 }
 
 int mb_xlnet_set_perm_mask(mb_xlnet_engine* e, const uint8_t* perm) {

@@ -312,7 +312,7 @@ int mb_bert_graph_stats(const mb_bert_engine* e, size_t* captures, size_t* launc
  *   New values never re-capture a graph: they reach the device with the step prologue, as the two groups' scalars do.
  * update_stats: the last enqueued update -- elements updated by riders inside the backward launches, elements updated by the sweep at the
  *   end of the step, and the number of segments of the map it ran under (0: the two parameter groups).  Any pointer may be NULL.
- * While a map is set MB_ADAMW_IN_WGRAD and MB_ADAMW_OVERLAP are off and mb_bert_train_step_dp returns MB_ERR_MODE. */
+ * While a map is set mb_bert_train_step_dp returns MB_ERR_MODE. */
 #define MB_UPDATE_CLASSES_MAX 32
 #define MB_UPDATE_SEGMENTS_MAX 128
 int mb_bert_set_update_map(mb_bert_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes);
@@ -322,8 +322,7 @@ int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept,
 
 /* Gradient-norm clipping inside mb_bert_train_step.  set_grad_clip: max_norm > 0 turns it on for every later step that ends with the
  * optimizer (m, v given); max_norm <= 0 or non-finite turns it off, the default.  Sticky, like set_update_values.  Such a step updates
- * no parameter before the whole gradient exists -- no riders in the backward launches, MB_ADAMW_IN_WGRAD and MB_ADAMW_OVERLAP off, so
- * update_stats reports ridden == 0 -- and between its backward and its sweep takes the norm of the flat gradient range [0,
+ * no parameter before the whole gradient exists -- no riders in the backward launches, so update_stats reports ridden == 0 -- and between its backward and its sweep takes the norm of the flat gradient range [0,
  * mb_bert_param_count) as mb_grad_clip_coef does, with the step's grad_scale, and multiplies the coefficient into the gradient scale the
  * sweep reads from device memory: one extra read of the gradient buffer, no pass that scales it.  After gradient-accumulation
  * micro-steps (no m, v: unaffected) the clipped quantity is the accumulated gradient.  On / off is part of a captured graph's identity;

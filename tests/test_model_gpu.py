@@ -604,21 +604,6 @@ def _trajectory(cdt, mode, nsteps=4, accum=1, layers=3, shapes=((5, 40), (5, 40)
                 shadow=m._core.shadow.clone(), losses=torch.stack(losses).cpu(), stats=stats, running=float(m.loss_running()))
 
 
-@pytest.mark.parametrize("cdt", [torch.float32, torch.bfloat16])
-def test_adamw_inside_the_weight_gradient_epilogue_changes_nothing(cdt, monkeypatch):
-    """EXPERIMENT MB_ADAMW_IN_WGRAD=1 (csrc/kernels.h EPI_WGRAD_ADAM): the layers' grouped weight-gradient launches apply
-    HF-AdamW to their own tiles instead of storing a gradient for the optimizer sweep.  Same arithmetic in the same order, so in
-    deterministic mode four steps (dropout on, schedule moving, two shapes = two captured graphs) end with the SAME BITS in the
-    parameters, both Adam moments, the bf16 shadow and the logits; the gradient buffer reads as zeros afterwards."""
-    monkeypatch.setenv("MB_DETERMINISTIC", "1")
-    ref = _trajectory(cdt, True)
-    monkeypatch.setenv("MB_ADAMW_IN_WGRAD", "1")
-    fused = _trajectory(cdt, True)
-    for k in ("p", "m", "v", "shadow", "logits"):
-        assert torch.equal(fused[k], ref[k]), "%s differs with the update inside the weight-gradient epilogue" % k
-    assert float(fused["g"].abs().max()) == 0.0 and fused["stats"] == ref["stats"]
-
-
 @pytest.mark.parametrize("cdt,tile", [(torch.float32, 128), (torch.bfloat16, 128), (torch.bfloat16, 256)])
 def test_adamw_riding_in_the_weight_gradient_launches_changes_nothing(cdt, tile, monkeypatch):
     """MB_ADAMW_RIDE=1 (csrc/kernels.h AdamRide): the grouped weight-gradient launch of layer l carries the HF-AdamW update of layer
@@ -811,25 +796,6 @@ def test_single_call_step_word_gradient_with_repeated_and_unique_token_ids():
         print("word-embedding gradient after %d accumulated steps: max |diff| %.3e (max |g| %.3e)" % (k + 1, err, scale))
         assert err <= 2e-6 * scale
         assert float(a[0].abs().max()) == 0.0             # padding_idx row
-
-
-def test_optimizer_chunks_on_a_side_stream_change_nothing(monkeypatch):
-    """MB_ADAMW_OVERLAP=C (an experiment kept behind its switch: DESIGN 4.5): the single-call step is cut into linear graphs at
-    every C-th layer of the backward and the AdamW of the finished chunk's GEMM weights runs on a side stream under the backward
-    of the layers below.  Same kernels on the same numbers in another order of launches: in deterministic mode the trajectory
-    (parameters, moments, bf16 shadow) is bit-identical to the plain step, through graph replays, a ragged batch and accumulation."""
-    monkeypatch.setenv("MB_DETERMINISTIC", "1")
-    shapes = ((8, 50), (8, 50), (5, 50), (8, 50))
-    ref = _trajectory(torch.bfloat16, True, nsteps=6, accum=1, layers=4, shapes=shapes)
-    acc_ref = _trajectory(torch.bfloat16, True, nsteps=4, accum=2, layers=4, shapes=((5, 40),))
-    for chunk in ("2", "4", "1"):
-        monkeypatch.setenv("MB_ADAMW_OVERLAP", chunk)
-        run = _trajectory(torch.bfloat16, True, nsteps=6, accum=1, layers=4, shapes=shapes)
-        for k in ("p", "m", "v", "shadow"):
-            assert torch.equal(run[k], ref[k]), "MB_ADAMW_OVERLAP=%s: %s differs from the plain step" % (chunk, k)
-        assert run["stats"][0] == ref["stats"][0]                  # as many captured step variants (each now a chain of graphs)
-    acc = _trajectory(torch.bfloat16, True, nsteps=4, accum=2, layers=4, shapes=((5, 40),))
-    assert torch.equal(acc["p"], acc_ref["p"]) and torch.equal(acc["shadow"], acc_ref["shadow"])
 
 
 def test_stale_gradients_survive_a_recreated_engine():
