@@ -146,9 +146,11 @@ PROTOTYPES = {
     "mb_xlnet_graph_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "mb_xlnet_trainable_count": (_sz, [_vp]),
     "mb_bert_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mb_bert_set_update_decay": (_i, [_vp, _i, _vp]),
     "mb_bert_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mb_bert_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
     "mb_xlnet_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mb_xlnet_set_update_decay": (_i, [_vp, _i, _vp]),
     "mb_xlnet_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mb_xlnet_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
     "mb_grad_clip_scratch_bytes": (_sz, [_sz]),

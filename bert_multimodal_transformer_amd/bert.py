@@ -593,9 +593,13 @@ class _Core(object):
     def _install_update_classes(self, opt):
         """classed optimizers (AdamW.flat_step_args with a "map"): the segment map goes to the engine when it changes -- it is part of a
         captured graph's identity -- and this step's per-class values every time (include/magbert_hip.h: mb_*_set_update_map /
-        _set_update_values).  The two-group optimizer clears a map another optimizer left behind; micro-steps leave it alone."""
+        _set_update_values), the no-decay marks of paired groups with the map (mb_*_set_update_decay).  The two-group optimizer clears a
+        map another optimizer left behind; micro-steps leave it alone."""
         seg = opt.get("map")
+        marks = opt.get("no_decay")          # paired groups (optimization.plan_paired_segments): per segment, 1 = does not decay
         key = None if seg is None else (tuple(seg[0]), tuple(seg[1]))
+        if key is not None and marks is not None and any(marks):
+            key += (tuple(1 if x else 0 for x in marks),)
         if key != getattr(self, "_update_map", None):
             if key is None:
                 _lib.check(self._fn("set_update_map")(self.handle, 0, 0, None, None))
@@ -603,6 +607,8 @@ class _Core(object):
                 bounds = (C.c_size_t * len(key[0]))(*key[0])
                 classes = (C.c_int * len(key[1]))(*key[1])
                 _lib.check(self._fn("set_update_map")(self.handle, max(key[1]) + 1, len(key[1]), bounds, classes))
+                if len(key) > 2:
+                    _lib.check(self._fn("set_update_decay")(self.handle, len(key[2]), (C.c_uint8 * len(key[2]))(*key[2])))
             self._update_map = key
         if key is not None:
             cv = opt["classes"]

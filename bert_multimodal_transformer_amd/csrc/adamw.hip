@@ -268,7 +268,7 @@ int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, co
     if (r.count < 0 || r.count > MB_SWEEP_PIECES_MAX || !cls) return MB_ERR_ARG;
     if (r.count && r.start4[0] != 0u) return MB_ERR_ARG;
     for (int k = 0; k < r.count; ++k)
-        if (r.start4[k + 1] < r.start4[k] || r.slot[k] >= MB_CLASSES_MAX) return MB_ERR_SHAPE;
+        if (r.start4[k + 1] < r.start4[k] || r.slot[k] >= 2 * MB_CLASSES_MAX) return MB_ERR_SHAPE;
     const size_t n4 = r.count ? r.start4[r.count] : 0;
     if (n4 == 0) return MB_OK;
     if ((sh_begin % 4) || (sh_end % 4) || (keep_begin % 4) || (keep_end % 4)) return MB_ERR_SHAPE;

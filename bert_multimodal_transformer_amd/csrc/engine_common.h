@@ -423,15 +423,24 @@ struct StepMixin {
     // first classed update and keeps until it is destroyed -- the workspace, whose size callers have planned with, stays as it was, and
     // so do the two slots of adam_state and the dropout keys behind them.  map_version joins the identity of a captured
     // graph: rider slices and sweep pieces are cut at the segment boundaries at capture time; the values never re-capture.
+    // No-decay marks (mb_*_set_update_decay): seg_nodecay[s] != 0 -- segment s updates with its class's lr / betas / eps / bias correction
+    // and weight_decay 0, so the decayed and the undecayed parameter group of one learning rate share a class.  The device table has two
+    // halves for that: slot c is class c as handed over, slot MB_CLASSES_MAX + c the same scalars with weight_decay = 0 (the prologue
+    // writes both from the one cls[c]); riders and sweep pieces of a marked segment read the upper slot, so no kernel looks at a mark.
+    // The marks are part of the map's identity (map_version), and set_update_map clears them.
     struct ClassVals { float lr, beta1, beta2, eps, weight_decay; int correct_bias; };
     int n_classes = 0, map_version = 0;
     std::vector<size_t> seg_bounds;
     std::vector<int> seg_class;
+    std::vector<uint8_t> seg_nodecay;
     std::vector<ClassVals> class_vals;
     AdamArgs* class_table = nullptr;
     size_t upd_ridden = 0, upd_swept = 0; int upd_segments = 0;       // the last enqueued update (mb_*_update_stats)
     int ensure_class_table() {          // (never inside a capture: train_step_impl calls it before the prologue)
-        if (!class_table) CK((int)hipMalloc((void**)&class_table, (size_t)MB_CLASSES_MAX * sizeof(AdamArgs)));
+        if (!class_table) {
+            CK((int)hipMalloc((void**)&class_table, (size_t)2 * MB_CLASSES_MAX * sizeof(AdamArgs)));
+            CK((int)hipMemset(class_table, 0, (size_t)2 * MB_CLASSES_MAX * sizeof(AdamArgs)));
+        }
         return MB_OK;
     }
     void free_class_table() { if (class_table) { hipFree(class_table); class_table = nullptr; } }
@@ -473,12 +482,13 @@ struct StepMixin {
     // the two launches between the backward and the sweep of a clipping step: every gradient of G[0, n) is final
     int enqueue_clip(const float* G, size_t n, char* ws, hipStream_t st) {
         CK(grad_sumsq(G, n, clip_partials(), st));
-        ClipTables t = {{adam_state(ws), n_classes > 0 ? class_state(ws) : nullptr}, {2, n_classes}};
+        // (both halves of the class table: slots [n_classes, MB_CLASSES_MAX) in between hold nothing anybody reads)
+        ClipTables t = {{adam_state(ws), n_classes > 0 ? class_state(ws) : nullptr}, {2, n_classes > 0 ? MB_CLASSES_MAX + n_classes : 0}};
         return grad_clip_finalize(clip_partials(), grad_norm_blocks(n), clip_params(), 0.f, 1.f, clip_record(), t, st);
     }
     int set_update_map(const std::vector<TensorInfo>& tensors, size_t n_update_end, int nc, int ns, const size_t* bounds, const int* classes) {
         if (nc == 0) {          // back to the two parameter groups (graphs captured for them were never dropped)
-            n_classes = 0; seg_bounds.clear(); seg_class.clear(); class_vals.clear();
+            n_classes = 0; seg_bounds.clear(); seg_class.clear(); seg_nodecay.clear(); class_vals.clear();
             return MB_OK;
         }
         if (nc < 0 || nc > MB_CLASSES_MAX || ns < 1 || ns > MB_SEGMENTS_MAX || !bounds || !classes) return MB_ERR_ARG;
@@ -492,11 +502,26 @@ struct StepMixin {
         }
         const bool same = nc == n_classes && (int)seg_class.size() == ns && std::equal(classes, classes + ns, seg_class.begin()) &&
                           std::equal(bounds, bounds + ns + 1, seg_bounds.begin());
-        if (same) return MB_OK;
-        n_classes = nc; seg_bounds.assign(bounds, bounds + ns + 1); seg_class.assign(classes, classes + ns); class_vals.clear();
+        const bool marked = std::any_of(seg_nodecay.begin(), seg_nodecay.end(), [](uint8_t x) { return x != 0; });
+        if (same && !marked) return MB_OK;
+        if (!same) class_vals.clear();
+        n_classes = nc; seg_bounds.assign(bounds, bounds + ns + 1); seg_class.assign(classes, classes + ns);
+        seg_nodecay.assign((size_t)ns, 0);          // a map starts without marks: every segment decays as its class says
         if (++map_version <= 0) map_version = 1;
         return MB_OK;
     }
+    int set_update_decay(int ns, const uint8_t* no_decay) {
+        if (n_classes == 0) return MB_ERR_MODE;          // marks belong to a map
+        if (ns != (int)seg_class.size() || !no_decay) return MB_ERR_ARG;
+        bool same = true;
+        for (int s = 0; s < ns; ++s) same = same && (no_decay[s] != 0) == (seg_nodecay[s] != 0);
+        if (same) return MB_OK;
+        for (int s = 0; s < ns; ++s) seg_nodecay[s] = no_decay[s] ? 1 : 0;
+        if (++map_version <= 0) map_version = 1;
+        return MB_OK;
+    }
+    // the slot of the device class table segment s reads: its class, or the class's weight_decay = 0 twin when the segment is marked
+    int seg_slot(size_t s) const { return seg_class[s] + (seg_nodecay[s] ? MB_CLASSES_MAX : 0); }
     int set_update_values(int nc, const float* lr, const float* beta1, const float* beta2, const float* eps, const float* weight_decay,
                           const int* correct_bias) {
         if (nc < 1 || nc != n_classes || !lr || !beta1 || !beta2 || !eps || !weight_decay || !correct_bias) return MB_ERR_ARG;
@@ -511,10 +536,10 @@ struct StepMixin {
         return MB_OK;
     }
     // riders of a classed step: a slice that ends at element `top` (exclusive) may reach down to the start of the segment that holds
-    // top - 1, and reads that segment's class
+    // top - 1, and reads that segment's slot of the class table
     void ride_segment(size_t top, size_t* floor, int* cls) const {
         const size_t s = (size_t)(std::upper_bound(seg_bounds.begin(), seg_bounds.end(), top - 1) - seg_bounds.begin()) - 1;
-        *floor = seg_bounds[s]; *cls = seg_class[s];
+        *floor = seg_bounds[s]; *cls = seg_slot(s);
     }
     // the sweep of a classed step: [b0, e0) and [b1, e1) (ascending, disjoint) cut at the segment boundaries
     int sweep_pieces(AdamPieces& out, size_t b0, size_t e0, size_t b1, size_t e1) const {
@@ -527,7 +552,7 @@ struct StepMixin {
                 if (lo >= hi) continue;
                 if (out.count >= MB_SWEEP_PIECES_MAX) return MB_ERR_ARG;
                 if ((lo | hi) % 4 || hi / 4 > 0xffffffffull || total4 + (hi - lo) / 4 > 0xffffffffull) return MB_ERR_SHAPE;
-                out.begin4[out.count] = (uint32_t)(lo / 4); out.start4[out.count] = (uint32_t)total4; out.slot[out.count] = (uint8_t)seg_class[s];
+                out.begin4[out.count] = (uint32_t)(lo / 4); out.start4[out.count] = (uint32_t)total4; out.slot[out.count] = (uint8_t)seg_slot(s);
                 total4 += (hi - lo) / 4;
                 out.start4[++out.count] = (uint32_t)total4;
             }

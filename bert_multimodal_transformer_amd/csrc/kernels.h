@@ -309,6 +309,8 @@ int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const Adam
 // a table of pieces (what the riders left, cut at the segment boundaries): piece k covers quads [begin4[k], begin4[k] + start4[k + 1] -
 // start4[k]) of the buffers, start4 being the running sum of the pieces' lengths, and reads its scalars from cls[slot[k]].  The class's
 // own weight_decay decides whether a piece decays (no n_decay here).  Same per-element arithmetic as adamw_sweep: the same bits.
+// The table has two halves of MB_CLASSES_MAX slots: slot MB_CLASSES_MAX + c is class c with weight_decay = 0, for segments marked
+// no-decay (mb_*_set_update_decay) -- the pieces and riders of such a segment name that slot, and no kernel knows about marks.
 #define MB_CLASSES_MAX 32
 #define MB_SEGMENTS_MAX 128
 #define MB_SWEEP_PIECES_MAX (MB_SEGMENTS_MAX + 2)
@@ -321,7 +323,7 @@ int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, co
 // alone); g needs 4-byte alignment only.  No atomics, fixed order: the same bits on every run.
 // grad_clip_finalize (one block): sum = the partials in index order; norm = grad_scale * sqrt(sum); coef = min(1, max_norm / (norm + 1e-6))
 // in double (torch.nn.utils.clip_grad_norm_; a non-finite norm gives what the arithmetic gives); out2 = {(float)norm, (float)coef}; then
-// tab[k][0 .. count[k]).grad_scale *= (float)coef for both tables (a null table is skipped; 256 entries in all at most).  dyn (device
+// tab[k][0 .. count[k]).grad_scale *= (float)coef for both tables (a null table is skipped; 256 entries in all at most: a classed step hands over 2 + both halves of its class table).  dyn (device
 // pointer, may be null): {max_norm, grad_scale} are read from there instead (replayed step graphs: PrologueArgs::clip).
 unsigned grad_norm_blocks(size_t n);
 int grad_sumsq(const float* g, size_t n, double* partial, hipStream_t st);
@@ -341,7 +343,7 @@ struct PrologueArgs {
     uint64_t seed, step;
     uint32_t* keys; int nsites;            // keys[2 * site + {0, 1}]
     AdamArgs adam[2]; AdamArgs* adam_dst;  // may be null
-    AdamArgs cls[MB_CLASSES_MAX]; AdamArgs* cls_dst; int ncls;      // update classes of a classed step: cls_dst[0 .. ncls) = cls (cls_dst may be null)
+    AdamArgs cls[MB_CLASSES_MAX]; AdamArgs* cls_dst; int ncls;      // update classes of a classed step: cls_dst[0 .. ncls) = cls, cls_dst[MB_CLASSES_MAX + c] = cls[c] with weight_decay 0 (2 * MB_CLASSES_MAX slots; may be null)
     float clip[2]; float* clip_dst;        // gradient-norm clipping: clip_dst[0 .. 1] = {max_norm, grad_scale} for grad_clip_finalize (may be null)
     uint32_t* zero_dw;                     // one dword cleared by the launch (the step's loss accumulator), may be null
     // modality tensors packed on the way in: src fp32 [rows][cols] (device or pinned host) -> dst [rows][pitch] of `dtype` (MAG's

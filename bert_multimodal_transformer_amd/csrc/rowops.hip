@@ -780,7 +780,12 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
             a.keys[2 * s + 1] = (uint32_t)(h >> 32);
         }
         if (a.adam_dst && threadIdx.x < 2) a.adam_dst[threadIdx.x] = a.adam[threadIdx.x];
-        if (a.cls_dst && (int)threadIdx.x < a.ncls) a.cls_dst[threadIdx.x] = a.cls[threadIdx.x];
+        if (a.cls_dst && (int)threadIdx.x < a.ncls) {          // both halves of the class table: the class, and its weight_decay = 0 twin
+            AdamArgs k = a.cls[threadIdx.x];
+            a.cls_dst[threadIdx.x] = k;
+            k.weight_decay = 0.f;
+            a.cls_dst[MB_CLASSES_MAX + threadIdx.x] = k;
+        }
         if (a.clip_dst && threadIdx.x < 2) a.clip_dst[threadIdx.x] = a.clip[threadIdx.x];
     }
     if (tid == 0 && a.zero_dw) *a.zero_dw = 0u;

@@ -668,6 +668,10 @@ int mb_xlnet_set_update_map(mb_xlnet_engine* e, int n_classes, int n_segments, c
     if (!e) return MB_ERR_ARG;
     return e->set_update_map(e->tensors, e->n_trainable, n_classes, n_segments, boundaries, classes);
 }
+int mb_xlnet_set_update_decay(mb_xlnet_engine* e, int n_segments, const uint8_t* no_decay) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_decay(n_segments, no_decay);
+}
 int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                                const float* weight_decay, const int* correct_bias) {
     if (!e) return MB_ERR_ARG;

@@ -61,6 +61,79 @@ def plan_update_segments(tensors, group_of_tensor, n_update_end):
     return boundaries, classes
 
 
+def pair_update_groups(hyper, hints=None):
+    """Which parameter groups may share an update class (include/magbert_hip.h: mb_*_set_update_decay).
+
+    hyper: per group (lr, betas, eps, correct_bias, weight_decay).  Two groups pair when lr, betas, eps and correct_bias are equal and
+    one of them has weight_decay == 0: the class carries the other's weight_decay, and the zero-decay group's segments are marked
+    no-decay.  hints (optional, one value per group, None = no hint) only choose among several possible partners: a decaying group
+    takes the first zero-decay group of its (lr, betas, eps, correct_bias) that has its hint, and what is left pairs in index order.
+    AdamW hands over the groups' initial_lr: during a warm-up from lr 0 every group has the same lr, and pairs made by index alone
+    would break -- and be planned again -- at the next step.  A group without a partner stays a class of its own.  Returns
+    (class_of_group, no_decay_of_group, members): class ids are dense, numbered by the smallest group index of the class; members[c] =
+    (the group whose values the class carries, its zero-decay partner or None)."""
+    decaying, zero = {}, {}
+    for g, (lr, betas, eps, correct_bias, wd) in enumerate(hyper):
+        key = (float(lr), tuple(float(b) for b in betas), float(eps), bool(correct_bias))
+        (zero if float(wd) == 0.0 else decaying).setdefault(key, []).append(g)
+    partner = {}
+    for key, gs in decaying.items():
+        free = list(zero.get(key, []))
+        if hints is not None:
+            for g in gs:
+                z = next((z for z in free if hints[g] is not None and hints[z] == hints[g]), None)
+                if z is not None:
+                    partner[g], partner[z] = z, g
+                    free.remove(z)
+        for g, z in zip([g for g in gs if g not in partner], free):
+            partner[g], partner[z] = z, g
+    class_of, no_decay, members = [None] * len(hyper), [False] * len(hyper), []
+    for g in range(len(hyper)):
+        if class_of[g] is not None:
+            continue
+        class_of[g] = len(members)
+        other = partner.get(g)
+        if other is None:
+            members.append((g, None))
+            continue
+        class_of[other] = len(members)
+        carrier, z = (other, g) if float(hyper[g][4]) == 0.0 else (g, other)
+        no_decay[z] = True
+        members.append((carrier, z))
+    return class_of, no_decay, members
+
+
+def plan_paired_segments(tensors, group_of_tensor, n_update_end, class_of_group, no_decay_of_group):
+    """plan_update_segments over the classes of paired groups (pair_update_groups): (boundaries, classes, no_decay_flags).  A segment
+    is a maximal run of consecutive tensors of one class AND one flag -- the decayed and the undecayed tensors of a class that touch
+    are two segments -- and flag s is 1 where segment s holds a zero-decay partner's tensors.  None under plan_update_segments' own
+    conditions, with the classes counted after pairing."""
+    if len(tensors) != len(group_of_tensor):
+        return None
+    rows = sorted((int(t[1]), int(t[2]), g) for t, g in zip(tensors, group_of_tensor) if int(t[1]) < n_update_end)
+    boundaries, classes, flags = [], [], []
+    cursor = 0
+    for off, numel, g in rows:
+        if isinstance(g, (list, tuple, set, frozenset)):
+            if len(g) != 1:
+                return None
+            g = next(iter(g))
+        if g is None or off != cursor or numel < 1 or not 0 <= int(g) < len(class_of_group):
+            return None
+        cursor = (off + numel + 63) // 64 * 64          # tensors are 64-float aligned in the flat layout
+        c, f = int(class_of_group[int(g)]), 1 if no_decay_of_group[int(g)] else 0
+        if not classes or classes[-1] != c or flags[-1] != f:
+            boundaries.append(off)
+            classes.append(c)
+            flags.append(f)
+    if cursor != n_update_end or not classes:
+        return None
+    boundaries.append(int(n_update_end))
+    if len(set(classes)) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
+        return None
+    return boundaries, classes, flags
+
+
 _NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")          # multimodal_driver.py:336
 _HEAD_MARKS = ("MAG.", "pooler.", "classifier.", "sequence_summary.", "logits_proj.")
 
@@ -246,9 +319,27 @@ class AdamW(torch.optim.Optimizer):
             if covered:
                 core.mark_grads_zero(True)
 
+    @staticmethod
+    def _hyper(group):
+        return (group["lr"], group["betas"], group["eps"], group["correct_bias"], group["weight_decay"])
+
+    def _pairs_hold(self, partners):
+        """the paired groups of a cached map still agree on lr / betas / eps / correct_bias, and the zero side is still zero"""
+        for g, z in partners:
+            if z is None:
+                continue
+            a, b = self._hyper(self.param_groups[g]), self._hyper(self.param_groups[z])
+            if float(a[0]) != float(b[0]) or tuple(a[1]) != tuple(b[1]) or float(a[2]) != float(b[2]) or bool(a[3]) != bool(b[3]) or float(b[4]) != 0.0:
+                return False
+        return True
+
     def _class_map(self, core):
-        """(boundaries, classes, groups) of this optimizer's groups over `core`'s flat layout -- the segment map of a classed step and
-        the parameter group behind every class -- or None (plan_update_segments).  The plan is fixed, so this is computed once."""
+        """(boundaries, classes, groups, no_decay, partners) of this optimizer's groups over `core`'s flat layout -- the segment map of a
+        classed step and the parameter group behind every class -- or None.  plan_update_segments comes first: every set of groups it
+        takes gets the map it always got, with no_decay = None.  Only when it declines are the groups paired (pair_update_groups,
+        plan_paired_segments): classes then stand for up to two groups, groups[c] is the one whose values class c carries, partners[c]
+        = (that group, its zero-decay partner or None), and no_decay marks the partner's segments.  The plan is computed once;
+        flat_step_args drops it when a pair no longer holds."""
         if id(core) not in self._class_maps:
             owner = {}
             for gi, group in enumerate(self.param_groups):
@@ -260,7 +351,15 @@ class AdamW(torch.optim.Optimizer):
             planned = plan_update_segments(core.tensors, [owner.get(t[1]) for t in core.tensors], n_end)
             if planned is not None:
                 groups = sorted(set(planned[1]))
-                planned = (planned[0], [groups.index(g) for g in planned[1]], groups)
+                planned = (planned[0], [groups.index(g) for g in planned[1]], groups, None, [(g, None) for g in groups])
+            else:
+                class_of, no_decay, members = pair_update_groups([self._hyper(g) for g in self.param_groups],
+                                                                 hints=[g.get("initial_lr") for g in self.param_groups])
+                paired = plan_paired_segments(core.tensors, [owner.get(t[1]) for t in core.tensors], n_end, class_of, no_decay)
+                if paired is not None:
+                    used = sorted(set(paired[1]))          # (groups without a tensor in this buffer leave holes in the class ids)
+                    planned = (paired[0], [used.index(c) for c in paired[1]], [members[c][0] for c in used], paired[2],
+                               [members[c] for c in used])
             self._class_maps[id(core)] = planned
         return self._class_maps[id(core)]
 
@@ -270,7 +369,10 @@ class AdamW(torch.optim.Optimizer):
         correction in both -- the scalars of that update.  For any other set of groups that covers the buffer's trainable range exactly
         once: the same dictionary with "map" = (boundaries, classes), the segment map (plan_update_segments), and "classes" = the
         per-class lists lr / beta1 / beta2 / eps / weight_decay / correct_bias of this step (include/magbert_hip.h:
-        mb_*_set_update_map / _set_update_values).  Either dictionary carries "max_grad_norm" (0.0 = no clipping), which the step installs
+        mb_*_set_update_map / _set_update_values).  More groups than the class table holds are paired first (_class_map): the
+        dictionary then also carries "no_decay", one flag per segment (mb_*_set_update_decay), and a class's values are those of the
+        pair's decaying group.  A cached pairing is checked on every call -- a pair whose groups no longer agree is planned again, which
+        may end in None.  Either dictionary carries "max_grad_norm" (0.0 = no clipping), which the step installs
         with mb_*_set_grad_clip; under allow_dp a clipping optimizer gets None -- the data-parallel single call has no norm of the reduced
         gradient, so that step is driven from Python.  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
         segments than the engine takes, fused_zero_grad off, data parallel -- whose step keeps its Python-driven exchange for classed
@@ -292,12 +394,16 @@ class AdamW(torch.optim.Optimizer):
                 two["max_grad_norm"] = self._clip_value()
             return two
         planned = self._class_map(core)
+        if planned is not None and not self._pairs_hold(planned[4]):
+            del self._class_maps[id(core)]          # a pair was broken by hand: pair and plan again with the groups as they are now
+            planned = self._class_map(core)
         if planned is None:
             return None
-        boundaries, classes, groups = planned
+        boundaries, classes, groups, no_decay, _ = planned
         gs = [self.param_groups[g] for g in groups]
+        marks = {} if no_decay is None else {"no_decay": list(no_decay)}
         return dict(m=core._adam_m, v=core._adam_v, grad_scale=float(self.grad_scale), map=(boundaries, classes),
-                    max_grad_norm=self._clip_value(),
+                    max_grad_norm=self._clip_value(), **marks,
                     classes=dict(lr=[float(g["lr"]) for g in gs], beta1=[float(g["betas"][0]) for g in gs],
                                  beta2=[float(g["betas"][1]) for g in gs], eps=[float(g["eps"]) for g in gs],
                                  weight_decay=[float(g["weight_decay"]) for g in gs],

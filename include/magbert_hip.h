@@ -305,6 +305,12 @@ int mb_bert_graph_stats(const mb_bert_engine* e, size_t* captures, size_t* launc
  *   n_classes = 0 (the other arguments are ignored) clears the map: the step of the two parameter groups again, the default.  The map is
  *   part of the identity of a captured step graph (rider slices and the sweep are cut at the segment boundaries); installing the map
  *   that is already in force changes nothing.
+ * set_update_decay (after set_update_map, which clears every mark): no_decay[s] != 0 marks segment s as one that does not decay -- it
+ *   updates with its class's lr / beta1 / beta2 / eps / correct_bias and weight_decay 0 (n_segments bytes, the map's count; host memory,
+ *   copied).  This lets the decayed and the undecayed parameter group of one learning rate share a class: layer-wise groups of a 24-layer
+ *   model are 52 groups and 26 classes.  The marks are part of the map's identity like the boundaries: a changed mark re-captures,
+ *   marks that are already in force change nothing.  NULL engine or marks, or another segment count than the map's: MB_ERR_ARG; no map
+ *   set: MB_ERR_MODE.
  * set_update_values: the hyper-parameters of every class (arrays of n_classes, which must be the map's; host memory, copied) that the
  *   following mb_bert_train_step calls consume, until the next call.  With a map set the scalar lr .. weight_decay and correct_bias arguments of the
  *   step are ignored -- opt_step, grad_scale and loss_scale are used as ever -- and inside a segment the class's own weight_decay decides
@@ -316,6 +322,7 @@ int mb_bert_graph_stats(const mb_bert_engine* e, size_t* captures, size_t* launc
 #define MB_UPDATE_CLASSES_MAX 32
 #define MB_UPDATE_SEGMENTS_MAX 128
 int mb_bert_set_update_map(mb_bert_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes);
+int mb_bert_set_update_decay(mb_bert_engine* e, int n_segments, const uint8_t* no_decay);
 int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                               const float* weight_decay, const int* correct_bias);
 int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments);
@@ -500,9 +507,10 @@ int mb_xlnet_load_batch(mb_xlnet_engine* e, const int64_t* input_ids, const floa
                         const void** staged6, void* stream);
 int mb_xlnet_graph_stats(const mb_xlnet_engine* e, size_t* captures, size_t* launches);
 size_t mb_xlnet_trainable_count(const mb_xlnet_engine* e);
-/* update classes of mb_xlnet_train_step: as mb_bert_set_update_map / _set_update_values / _update_stats above; the map covers
+/* update classes of mb_xlnet_train_step: as mb_bert_set_update_map / _set_update_decay / _set_update_values / _update_stats above; the map covers
  * [0, mb_xlnet_trainable_count), and the sweep of a classed step is one launch here too */
 int mb_xlnet_set_update_map(mb_xlnet_engine* e, int n_classes, int n_segments, const size_t* boundaries, const int* classes);
+int mb_xlnet_set_update_decay(mb_xlnet_engine* e, int n_segments, const uint8_t* no_decay);
 int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                                const float* weight_decay, const int* correct_bias);
 int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments);

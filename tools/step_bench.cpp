@@ -14,7 +14,8 @@
 //   --graph: 0 forward/backward/AdamW calls, 1 mb_bert_train_step hipGraph replay, 2 mb_bert_train_step stream launches
 //   --layer_decay D, --head_lr_mult K (each off at 1; --graph 1|2, no --dp): per-group learning rates as update classes
 //            (mb_*_set_update_map / _set_update_values) -- layer l of N at lr * D^(N - l), the embeddings at lr * D^(N + 1), MAG / pooler /
-//            heads at K * lr, every learning rate split by the no-decay rule while that fits the class table (one class per depth otherwise)
+//            heads at K * lr, every learning rate split by the no-decay rule: two classes per depth while that fits the class table, one
+//            class per depth with no-decay marks on the undecayed segments otherwise (mb_*_set_update_decay) -- the same update
 //   --max_grad_norm X (--graph 1|2, no --dp; 0 = off): gradient-norm clipping inside the step (mb_*_set_grad_clip); the norm and coefficient
 //            of the last update are printed
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
@@ -156,7 +157,11 @@ int main(int argc, char** argv) {
     if (classed) {
         if (!graph || dp) { fprintf(stderr, "--layer_decay / --head_lr_mult: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
         // depth 0 = embeddings (and any other encoder tensor), l + 1 = layer l, layers + 1 = MAG / pooler / heads
+        // Two classes per depth (decayed / not) while they fit the table; deeper models share one class per depth and mark the
+        // no-decay segments (mb_*_set_update_decay) -- the same update either way
         const bool split = 2 * (layers + 2) <= MB_UPDATE_CLASSES_MAX;
+        if (layers + 2 > MB_UPDATE_CLASSES_MAX) { fprintf(stderr, "--layer_decay / --head_lr_mult: at most %d layers\n", MB_UPDATE_CLASSES_MAX - 2); return 1; }
+        std::vector<uint8_t> marks;
         std::vector<int> slot_of(2 * (layers + 2), -1);
         std::vector<size_t> bounds; std::vector<int> cls;
         std::vector<float> c_lr, c_b1, c_b2, c_eps, c_wd; std::vector<int> c_cb;
@@ -180,14 +185,17 @@ int main(int argc, char** argv) {
                 c_lr.push_back(depth == layers + 1 ? (float)(lr * head_lr_mult) : (float)(lr * pow(layer_decay, layers + 1 - depth)));
                 c_b1.push_back(b1); c_b2.push_back(b2); c_eps.push_back(eps); c_wd.push_back((split && no_decay) ? 0.f : wd); c_cb.push_back(1);
             }
-            if (cls.empty() || cls.back() != slot_of[key]) { bounds.push_back(off); cls.push_back(slot_of[key]); }
+            const uint8_t mark = (!split && no_decay) ? 1 : 0;
+            if (cls.empty() || cls.back() != slot_of[key] || marks.back() != mark) { bounds.push_back(off); cls.push_back(slot_of[key]); marks.push_back(mark); }
             end = (off + numel + 63) / 64 * 64;
         }
         bounds.push_back(end);
         n_segments = (int)cls.size();
         if (xl) { MCK(mb_xlnet_set_update_map(ex, n_classes, n_segments, bounds.data(), cls.data()));
+                  if (!split) MCK(mb_xlnet_set_update_decay(ex, n_segments, marks.data()));
                   MCK(mb_xlnet_set_update_values(ex, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
         else { MCK(mb_bert_set_update_map(e, n_classes, n_segments, bounds.data(), cls.data()));
+               if (!split) MCK(mb_bert_set_update_decay(e, n_segments, marks.data()));
                MCK(mb_bert_set_update_values(e, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
     }
     if (max_grad_norm > 0.0) {
