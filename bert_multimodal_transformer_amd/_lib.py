@@ -149,6 +149,10 @@ PROTOTYPES = {
     "mb_bert_set_update_decay": (_i, [_vp, _i, _vp]),
     "mb_bert_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mb_bert_update_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i)]),
+    "mb_bert_set_update_frozen": (_i, [_vp, _i, _vp]),
+    "mb_bert_freeze_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
+    "mb_xlnet_set_update_frozen": (_i, [_vp, _i, _vp]),
+    "mb_xlnet_freeze_stats": (_i, [_vp, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
     "mb_xlnet_set_update_map": (_i, [_vp, _i, _i, _vp, _vp]),
     "mb_xlnet_set_update_decay": (_i, [_vp, _i, _vp]),
     "mb_xlnet_set_update_values": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -593,13 +593,17 @@ class _Core(object):
     def _install_update_classes(self, opt):
         """classed optimizers (AdamW.flat_step_args with a "map"): the segment map goes to the engine when it changes -- it is part of a
         captured graph's identity -- and this step's per-class values every time (include/magbert_hip.h: mb_*_set_update_map /
-        _set_update_values), the no-decay marks of paired groups with the map (mb_*_set_update_decay).  The two-group optimizer clears a
-        map another optimizer left behind; micro-steps leave it alone."""
+        _set_update_values), the no-decay marks of paired groups and the frozen marks of tensors no group holds with the map
+        (mb_*_set_update_decay / _set_update_frozen).  The two-group optimizer clears a map another optimizer left behind; micro-steps
+        leave it alone."""
         seg = opt.get("map")
         marks = opt.get("no_decay")          # paired groups (optimization.plan_paired_segments): per segment, 1 = does not decay
+        frozen = opt.get("frozen")           # tensors no parameter group holds: per segment, 1 = frozen
         key = None if seg is None else (tuple(seg[0]), tuple(seg[1]))
-        if key is not None and marks is not None and any(marks):
-            key += (tuple(1 if x else 0 for x in marks),)
+        if key is not None and ((marks is not None and any(marks)) or (frozen is not None and any(frozen))):
+            key += (tuple(1 if x else 0 for x in (marks or [0] * len(seg[1]))),)
+        if key is not None and frozen is not None and any(frozen):
+            key += (tuple(1 if x else 0 for x in frozen),)
         if key != getattr(self, "_update_map", None):
             if key is None:
                 _lib.check(self._fn("set_update_map")(self.handle, 0, 0, None, None))
@@ -607,8 +611,10 @@ class _Core(object):
                 bounds = (C.c_size_t * len(key[0]))(*key[0])
                 classes = (C.c_int * len(key[1]))(*key[1])
                 _lib.check(self._fn("set_update_map")(self.handle, max(key[1]) + 1, len(key[1]), bounds, classes))
-                if len(key) > 2:
+                if len(key) > 2 and any(key[2]):
                     _lib.check(self._fn("set_update_decay")(self.handle, len(key[2]), (C.c_uint8 * len(key[2]))(*key[2])))
+                if len(key) > 3:
+                    _lib.check(self._fn("set_update_frozen")(self.handle, len(key[3]), (C.c_uint8 * len(key[3]))(*key[3])))
             self._update_map = key
         if key is not None:
             cv = opt["classes"]
@@ -630,6 +636,13 @@ class _Core(object):
         ridden, swept, segs = C.c_size_t(), C.c_size_t(), C.c_int()
         _lib.check(self._fn("update_stats")(self.handle, C.byref(ridden), C.byref(swept), C.byref(segs)))
         return ridden.value, swept.value, segs.value
+
+    def freeze_stats(self):
+        """(elements in frozen segments, weight-gradient launches left out, 1 when the embedding backward / word scatter was left out)
+        of the last single-call step (include/magbert_hip.h: mb_*_freeze_stats); all zero without frozen tensors"""
+        elems, wgrads, emb = C.c_size_t(), C.c_int(), C.c_int()
+        _lib.check(self._fn("freeze_stats")(self.handle, C.byref(elems), C.byref(wgrads), C.byref(emb)))
+        return elems.value, wgrads.value, emb.value
 
     def stage_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, loss_scale=1.0, mode=1):
         """forward + MSE + backward of one training step cut at the backward stages (include/magbert_hip.h: mb_bert_stage_forward /
@@ -1031,6 +1044,9 @@ class _MagBertBase(nn.Module):
         return read_config_beside(path, num_labels) if cls.base_model_prefix == "bert" else None
 
 
+_NEVER_FROZEN = ("MAG.", "pooler.", "classifier.", "sequence_summary.", "logits_proj.")
+
+
 class _FusedStep(object):
     """Fused training surface shared by MAG_BertForSequenceClassification and MAG_XLNetForSequenceClassification
     (what the bundled driver's train_epoch and bench.py call instead of the reference's five-line step)."""
@@ -1050,6 +1066,42 @@ class _FusedStep(object):
         core.forward(input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, True)
         core._backward(None, loss_scale)
         return core.loss_buf[0]
+
+    def freeze(self, embeddings=False, layers=()):
+        """The usual fine-tuning recipe: requires_grad = False on the embedding tensors (embeddings=True: MAG-BERT's word, position and
+        token-type tables and their LayerNorm, MAG-XLNet's word table and its never-trained mask_emb) and on every parameter of the named encoder layers -- `layers` is
+        an int (the lowest N layers) or an iterable of layer indices.  The MAG gate, the pooler / sequence summary and the classifier
+        cannot be frozen this way.  Returns the names, sorted.  Build the optimizer afterwards: optimizer_grouped_parameters and
+        layerwise_lr_groups leave such parameters out, AdamW then treats them as HF AdamW treats a parameter without a gradient (no
+        state, never touched), and the single-call step skips the weight-gradient launches of fully frozen layers and the embedding
+        backward.  The explicit passes (training_step, forward + backward) still compute every gradient."""
+        n_layers = self._core.n_layers
+        want = set(range(int(layers))) if isinstance(layers, int) else set(int(l) for l in layers)
+        if any(l < 0 or l >= n_layers for l in want):
+            raise ValueError("layers must lie in [0, %d), got %s" % (n_layers, sorted(want)))
+        marks = tuple(m % l for l in sorted(want) for m in ("encoder.layer.%d.", "transformer.layer.%d."))
+        emb = ("bert.embeddings.", "transformer.word_embedding.", "transformer.mask_emb") if embeddings else ()
+        names = []
+        for n, p in self.named_parameters():
+            if any(n.startswith(mk) or ("." + mk) in n for mk in _NEVER_FROZEN):
+                continue
+            if any(mk in n for mk in marks) or any(n.startswith(mk) for mk in emb):
+                p.requires_grad_(False)
+                names.append(n)
+        return sorted(names)
+
+    def unfreeze(self):
+        """requires_grad = True again on everything freeze() may have frozen; returns the names that changed.  An optimizer built
+        before keeps treating them as frozen: build a new one.  Their `.grad` views are cleared: the explicit passes compute every gradient,
+        a frozen tensor's too, and no optimizer zeroed what they left there."""
+        names = []
+        for n, p in self.named_parameters():
+            if not p.requires_grad:
+                p.requires_grad_(True)
+                if p.grad is not None:          # what the explicit passes accumulated there while nobody consumed it
+                    p.grad.zero_()
+                names.append(n)
+        return sorted(names)
 
     def train_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, optimizer=None,
                    loss_scale=1.0, graph=None):

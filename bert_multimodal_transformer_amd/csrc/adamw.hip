@@ -218,20 +218,44 @@ int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const Adam
 // The sweep of a classed step (kernels.h AdamPieces): adamw_sweep_kernel with its ranges read from a table of up to MB_SWEEP_PIECES_MAX
 // pieces whose running sums the host laid out, every piece with its class's slot of `cls`, and the class's weight_decay in place of
 // "i < n_decay".  A block walks the pieces in front of its own with scalar loads of the kernel arguments only.
+// Pieces [clear_first, count) are clear-only (slot MB_PIECE_CLEAR, frozen segments): zeros over their gradient ranges, by blocks of their own.
 template <bool NT>
 __global__ void __launch_bounds__(256) adamw_sweep_classed_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                                   float* __restrict__ v, bf16* __restrict__ shadow, const AdamPieces R,
                                                                   size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end,
-                                                                  const AdamArgs* __restrict__ cls, WordSkip ws) {
+                                                                  const AdamArgs* __restrict__ cls, WordSkip ws, unsigned upd_blocks) {
     constexpr int UNR = 2;
-    const size_t total4 = R.start4[R.count];
-    const size_t per = ((total4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    if (blockIdx.x >= upd_blocks) {
+        // Clear-only pieces (MB_PIECE_CLEAR, pieces [clear_first, count)): blocks of their own behind the update's, which walk the clear
+        // pieces laid end to end the same way and store zeros over the gradient -- no parameter, moment or shadow byte is touched.
+        // (As a branch inside the update loop below the same stores cost that loop 22 registers: 90 against 68 VGPRs, 5 resident
+        //  blocks per CU instead of 7.)
+        const size_t c0 = R.start4[R.clear_first], ctotal4 = R.start4[R.count] - c0;
+        const unsigned nclr = gridDim.x - upd_blocks;
+        const size_t cper = ((ctotal4 + nclr - 1) / nclr + 255) / 256 * 256;
+        const size_t cb = c0 + (size_t)(blockIdx.x - upd_blocks) * cper, ce = min(c0 + ctotal4, cb + cper);
+#pragma unroll 1
+        for (int k = R.clear_first; k < R.count; ++k) {
+            const size_t off = R.start4[k], nxt = R.start4[k + 1];
+            if (nxt <= cb) continue;
+            if (off >= ce) break;
+            const size_t lo = max(cb, off), hi = min(ce, nxt);
+            const size_t base4 = (size_t)R.begin4[k] - off;
+            for (size_t i4 = base4 + lo + threadIdx.x; i4 < base4 + hi; i4 += 256) {
+                if constexpr (NT) __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, (f32x4*)(g + i4 * 4));
+                else *(f32x4*)(g + i4 * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        return;
+    }
+    const size_t total4 = R.start4[R.clear_first];
+    const size_t per = ((total4 + upd_blocks - 1) / upd_blocks + 255) / 256 * 256;
     const size_t vb = (size_t)blockIdx.x * per, ve = min(total4, vb + per);
     const bool skip_on = ws.stamp != nullptr && ws.state[1] != 0u;
     const uint32_t stamp_no = skip_on ? ws.state[0] : 0u;
     const size_t all = ~(size_t)0;
 #pragma unroll 1
-    for (int k = 0; k < R.count; ++k) {
+    for (int k = 0; k < R.clear_first; ++k) {
         const size_t off = R.start4[k], nxt = R.start4[k + 1];
         if (nxt <= vb) continue;
         if (off >= ve) break;
@@ -265,12 +289,12 @@ __global__ void __launch_bounds__(256) adamw_sweep_classed_kernel(float* __restr
 
 int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
                         size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st) {
-    if (r.count < 0 || r.count > MB_SWEEP_PIECES_MAX || !cls) return MB_ERR_ARG;
+    if (r.count < 0 || r.count > MB_SWEEP_PIECES_MAX || r.clear_first < 0 || r.clear_first > r.count || !cls) return MB_ERR_ARG;
     if (r.count && r.start4[0] != 0u) return MB_ERR_ARG;
-    for (int k = 0; k < r.count; ++k)
-        if (r.start4[k + 1] < r.start4[k] || r.slot[k] >= 2 * MB_CLASSES_MAX) return MB_ERR_SHAPE;
-    const size_t n4 = r.count ? r.start4[r.count] : 0;
-    if (n4 == 0) return MB_OK;
+    for (int k = 0; k < r.count; ++k)          // update pieces first, every clear-only piece behind them
+        if (r.start4[k + 1] < r.start4[k] || (k < r.clear_first ? r.slot[k] >= 2 * MB_CLASSES_MAX : r.slot[k] != MB_PIECE_CLEAR)) return MB_ERR_SHAPE;
+    const size_t n4 = r.count ? r.start4[r.clear_first] : 0, c4 = r.count ? r.start4[r.count] - n4 : 0;
+    if (n4 + c4 == 0) return MB_OK;
     if ((sh_begin % 4) || (sh_end % 4) || (keep_begin % 4) || (keep_end % 4)) return MB_ERR_SHAPE;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MB_ERR_SHAPE;
     if (skip.stamp && (!skip.state || skip.row_len == 0 || (skip.begin | skip.end | skip.row_len) % 4 || skip.end < skip.begin ||
@@ -285,10 +309,13 @@ int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, co
     static int nt = -1, vgrid = 0;
     if (nt < 0) { const char* e = getenv("MB_ADAMW_NT"); nt = e ? atoi(e) : 1; const char* g2 = getenv("MB_ADAMW_GRID"); vgrid = g2 ? atoi(g2) : 0; }
     if (vgrid > 0 && (unsigned)vgrid < grid) grid = (unsigned)vgrid;
-    if (nt) hipLaunchKernelGGL(adamw_sweep_classed_kernel<true>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
-                               keep_begin, keep_end, cls, skip);
-    else hipLaunchKernelGGL(adamw_sweep_classed_kernel<false>, dim3(grid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
-                            keep_begin, keep_end, cls, skip);
+    // clear-only pieces: 2,048 quads per block (32 KB of zeros), one block per CU at most -- a few tensors of biases and LayerNorm weights
+    unsigned cgrid = (unsigned)((c4 + 2047) / 2048);
+    if (cgrid > 256) cgrid = 256;
+    if (nt) hipLaunchKernelGGL(adamw_sweep_classed_kernel<true>, dim3(grid + cgrid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
+                               keep_begin, keep_end, cls, skip, grid);
+    else hipLaunchKernelGGL(adamw_sweep_classed_kernel<false>, dim3(grid + cgrid), dim3(256), 0, st, p, g, m, v, (bf16*)shadow, r, sh_begin, sh_end,
+                            keep_begin, keep_end, cls, skip, grid);
     return (int)hipGetLastError();
 }
 

@@ -32,6 +32,9 @@ struct mb_bert_engine : StepMixin {
     size_t layer_begin(int l) const { return lo[l].wqkv; }
     size_t layers_end() const { return wp; }
     int width() const { return c.hidden_size; }
+    size_t layer_end(int l) const { return l + 1 < c.num_layers ? lo[l + 1].wqkv : wp; }
+    // frozen marks (StepMixin::seg_frozen): the five embedding tensors are all frozen -- a single-call step runs no embedding backward
+    bool embed_all_frozen() const { return range_frozen(word, mag_whv) && range_frozen(emb_lnw, bp); }
     // workspace
     MagWs mw;
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
@@ -466,6 +469,7 @@ int mb_bert_bind(mb_bert_engine* e, float* params, float* grads, void* shadow, v
     if (e->c.dtype == DT_BF16 && !shadow) return MB_ERR_ARG;
     e->P = params; e->G = grads; e->SH = (char*)shadow; e->ws = (char*)workspace;
     e->grads_zero = false;                 // a newly bound gradient buffer: nothing is known about its contents
+    e->frz_dirty = true;
     e->stamp_live = e->word_zero = false; e->sweep_no = 1;      // (and a workspace that is cleared before its first pass)
     e->ws_zeroed = false; e->padT = -1;
     e->drop_graphs();                         // captured against the old buffers
@@ -582,7 +586,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
         const AdamArgs* dyn = e->adam_state(e->ws);
         if (e->n_classes > 0) {
             size_t sb = 0; int cl = 0;
-            e->ride_segment(e->ride_cursor, &sb, &cl);
+            if (!e->ride_segment(e->ride_cursor, floor, &sb, &cl)) return r;          // (hops over frozen layers; false: nothing left for this host)
             floor = std::max(floor, sb); dyn = e->class_state(e->ws) + cl;
         }
         size_t take = std::min(e->ride_cursor - floor, budget) / 1024 * 1024;
@@ -652,6 +656,10 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                               wgrad_args(H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H),
                               wgrad_args(3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H)};
             const bool grouped = e->grouped;
+            // frozen marks: a single-call step leaves out the weight gradients of a layer whose four GEMM weights nobody updates (the
+            // riders that launch would have carried fall to later hosts or to the sweep); the input-gradient chain runs as always
+            const bool wfrozen = e->skipping() && e->unwritten(o.wqkv, e->layer_end(l));
+            if (wfrozen) ++e->frz_wgrad_skipped;
             if (grouped)
                 for (GemmArgs& a : wg) a.overwrite = e->ow_pass ? 1 : 0;       // whole-tile, no split-K launches only
             // dX = dY . W + R (GEMM_NN, EPI_ADD_RES), with riders when the launch is the 64 x 64 three-slot kernel and leaves block slots free
@@ -667,10 +675,10 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             int wtile = e->group_wgrad;
             if (grouped && wtile == 256 && !gemm_grouped_tn_ok(dt, wg, 4, 256)) wtile = 128;      // (fewer than three k stages: the 128 x 128 kernel)
             if (grouped && !gemm_grouped_tn_ok(dt, wg, 4, wtile)) return MB_ERR_SHAPE;
-            if (!grouped) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
             // du = (dzd . W2) * gelu'(u), with the intermediate bias gradient (column sums of du) fused into the epilogue
             CK(dgrad_ride(EPI_DGELU, T, I, H, dzdA, H, e->W(o.w2), I, du, I, ws + w.u, I, G + o.b1));
-            if (!grouped) CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, st));
             CK(dgrad_ride(EPI_ADD_RES, T, H, I, du, I, e->W(o.w1), H, dy1, H, dsA, H, nullptr));
             // LN1 + dropout backward
             Prefetch pf_attn = {e->prefetch ? e->W(o.wqkv) : nullptr, (size_t)4 * H * H * (dt == DT_BF16 ? 2 : 4), nullptr};
@@ -685,7 +693,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                     // ... Wqkv | Wo for the attention-side dgrads, and with the loads that leaves over the q | k | v (+ context)
                                     // rows this layer saved in the forward, which the attention backward two launches on finds in HBM
                                     pf_attn));
-            if (!grouped) CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.ctx, H, G + o.wo, H, st));
             e->lnp_nblk = nblk;
             if (!defer_ln) {
                 float* const dst6[6] = {G + o.ln2w, G + o.ln2b, G + o.b2, G + o.ln1w, G + o.ln1b, G + o.bo};
@@ -720,7 +728,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                   e->attn_stats(w)));
             // riders: an optimizer update in the empty slots of this launch (take_ride, below the loop header)
             AdamRide ride = {};
-            if (grouped) {
+            if (grouped && !wfrozen) {
                 int tiles = 0;
                 const int bm = wtile == 256 ? 256 : wtile, bn = wtile == 256 ? 128 : wtile;
                 for (const GemmArgs& a : wg) tiles += (a.M / bm) * (a.N / bn);
@@ -732,9 +740,9 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             }
             if (grouped) {
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], st));
-                CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, ride.blocks ? &ride : nullptr));
+                if (!wfrozen) CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, ride.blocks ? &ride : nullptr));
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], st));
-            } else {
+            } else if (!wfrozen) {
                 CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, st));
             }
             CK(dgrad_ride(EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, dsB, H, nullptr));
@@ -754,9 +762,15 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                             G + e->mag_bv, G + e->mag_wa, G + e->mag_ba, G + e->mag_lnw, G + e->mag_lnb, T, H, c.visual_dim,
                             c.acoustic_dim, true, st, acc, true, mpa, mpb, &mblk, e->ow_pass));
             int eblk = 0;
+            // frozen marks, single-call step: no word scatter into a frozen table (the launch runs as it does for inputs_embeds), and no
+            // launch at all when nobody updates any of its five outputs
+            const bool word_frozen = e->skipping() && e->unwritten(e->word, e->pos);
+            const bool emb_frozen = e->skipping() && e->unwritten(e->word, e->mag_whv) && e->unwritten(e->emb_lnw, e->bp);
+            if (emb_frozen) e->frz_embed_skipped = 1;
+            else
             CK(embed_ln_backward(dt, de, e->ids, e->seg, e->ids ? P + e->word : e->emb_in, P + e->pos, P + e->type, P + e->emb_lnw,
                                  (const float*)(ws + e->ws_emb_st), (const float*)(ws + e->ws_emb_st) + T,
-                                 (float*)(ws + e->ws_dsum), e->ids ? G + e->word : nullptr, G + e->pos, G + e->type, G + e->emb_lnw,
+                                 (float*)(ws + e->ws_dsum), (e->ids && !word_frozen) ? G + e->word : nullptr, G + e->pos, G + e->type, G + e->emb_lnw,
                                  G + e->emb_lnb, B, L, H, c.pad_token_id, e->key(SITE_EMB, c.hidden_dropout), st, e->pos_ids, acc,
                                  (float*)(ws + e->ws_lnp_a) + (size_t)(NL + 1) * e->lnp_stride, &eblk,
                                  (float*)(ws + e->ws_lnp_b) + (size_t)(NL + 1) * e->lnp_stride,
@@ -775,8 +789,8 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                 float* const m6[6] = {G + e->mag_bhv, G + e->mag_bha, G + e->mag_bv, G + e->mag_ba, G + e->mag_lnw, G + e->mag_lnb};
                 for (int q = 0; q < 6; ++q) dst.d[NL - first][q] = m6[q];
                 dst.nblk[NL - first] = mblk; dst.nblk[NL + 1 - first] = eblk;         // (their kernels: 8 rows per block; ln_bwd: 16)
-                dst.d[NL + 1 - first][0] = G + e->emb_lnw; dst.d[NL + 1 - first][1] = G + e->emb_lnb;   // (rows 0 / 1 of set a)
-                if (e->pos_ids == nullptr) {       // the one-launch embedding backward: token-type sums in row 2 of set a / row 0 of set b
+                if (!emb_frozen) { dst.d[NL + 1 - first][0] = G + e->emb_lnw; dst.d[NL + 1 - first][1] = G + e->emb_lnb; }   // (rows 0 / 1 of set a)
+                if (e->pos_ids == nullptr && !emb_frozen) {       // the one-launch embedding backward: token-type sums in row 2 of set a / row 0 of set b
                     dst.d[NL + 1 - first][2] = G + e->type; dst.d[NL + 1 - first][3] = G + e->type + H;
                 }
                 CK(ln_reduce_partials_layers((const float*)(ws + e->ws_lnp_a) + (size_t)first * e->lnp_stride,
@@ -820,6 +834,15 @@ static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* l
                       (e->group_wgrad == 128 || e->group_wgrad == 256) && !clip;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wp;
+    // frozen marks: what this step's backward will not write (StepMixin::frz_unwritten) -- the GEMM weights of fully frozen layers, a
+    // frozen word table, every embedding tensor when all five are frozen.  The riders and the sweep are cut around them.
+    e->frz_unwritten.clear(); e->ride_hopped = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
+    e->frz_elems = e->any_frozen ? e->frozen_total() : 0;
+    if (e->skipping()) {
+        for (int l = 0; l < NL; ++l) if (e->range_frozen(e->lo[l].wqkv, e->layer_end(l))) e->note_unwritten(e->lo[l].wqkv, e->layer_end(l));
+        if (e->embed_all_frozen()) { e->note_unwritten(e->word, e->mag_whv); e->note_unwritten(e->emb_lnw, e->bp); }
+        else if (e->range_frozen(e->word, e->pos)) e->note_unwritten(e->word, e->pos);
+    }
     // backward stages: 0 = head, 1 .. NL = layers NL-1 .. 0, NL+1 = MAG + embeddings
     const int rb = mb_bert_backward(e, nullptr, lab, loss_scale, 0, NL + 2, st);
     e->ride_m = e->ride_v = nullptr;
@@ -829,15 +852,15 @@ static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* l
         const size_t nd = e->n_decay, n = e->n_params;
         if (clip) CK(e->enqueue_clip(e->G, n, ws, st));      // the whole gradient is final: its norm, and the coefficient into the scalars the sweep below reads
         CK(e->prof_mark(2 * NL, st));
-        e->upd_ridden = ride ? e->wp - e->ride_cursor : 0; e->upd_swept = n - e->upd_ridden;
+        e->upd_ridden = ride ? e->wp - e->ride_cursor - e->ride_hopped : 0; e->upd_swept = n - e->upd_ridden - e->frz_elems;
         e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
         if (e->n_classes > 0) {
             // Classed step (kernels.h AdamPieces): the same ranges cut at the segment boundaries, every piece with its class's slot, ONE
             // launch; the word rows and the keep range as below
             AdamPieces pieces;
-            CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wp, e->wp, n));
-            const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
             const bool keep = e->keep_in_step();
+            CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wp, e->wp, n, true, keep ? e->stale_begin : 0, keep ? e->stale_end : 0));
+            const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
             WordSkip ws_ = {};
             if (skip) ws_ = WordSkip{e->stamp_table(ws), e->stamp_state(ws), e->word, e->word + (size_t)e->c.vocab_size * e->c.hidden_size,
                                       (uint32_t)e->c.hidden_size};
@@ -893,6 +916,14 @@ int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr,
                               const float* weight_decay, const int* correct_bias) {
     if (!e) return MB_ERR_ARG;
     return e->set_update_values(n_classes, lr, beta1, beta2, eps, weight_decay, correct_bias);
+}
+int mb_bert_set_update_frozen(mb_bert_engine* e, int n_segments, const uint8_t* frozen) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_frozen(n_segments, frozen);
+}
+int mb_bert_freeze_stats(const mb_bert_engine* e, size_t* frozen_elems, int* wgrad_launches_skipped, int* embed_skipped) {
+    if (!e) return MB_ERR_ARG;
+    return e->freeze_stats(frozen_elems, wgrad_launches_skipped, embed_skipped);
 }
 int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments) {
     if (!e) return MB_ERR_ARG;
@@ -1066,12 +1097,14 @@ int mb_bert_mark_grads_zero(mb_bert_engine* e, int known_zero) {
     if (!e) return MB_ERR_ARG;
     e->grads_zero = known_zero != 0;
     if (!known_zero) e->stamp_live = e->word_zero = false;      // somebody else is writing gradients (StepMixin::stamp_live)
+    if (!known_zero) e->frz_dirty = true;                       // ... maybe into frozen segments
     if (known_zero) e->grads_stale = false;       // the caller zeroed the whole buffer itself
     return MB_OK;
 }
 int mb_bert_distrust_word_stamps(mb_bert_engine* e) {
     if (!e) return MB_ERR_ARG;
     e->stamp_live = e->word_zero = false;
+    e->frz_dirty = true;          // (torch wrote into the gradient buffer: maybe into frozen segments)
     return MB_OK;
 }
 size_t mb_bert_word_skip_updates(const mb_bert_engine* e) { return e ? e->skip_updates : 0; }

@@ -218,6 +218,7 @@ struct StepGraph {
     const void* tag;                                // whose events the graphs' nodes record (the mb_comm of a data-parallel step), else null
     std::vector<hipGraph_t> graph; std::vector<hipGraphExec_t> exec;
     size_t ridden = 0, swept = 0; int segments = 0; // what the captured update covers (StepMixin::upd_*: a replay enqueues nothing on the host)
+    size_t frozen = 0; int wgrad_skipped = 0, embed_skipped = 0;      // ... and what it left out (StepMixin::frz_*)
     int clip = 0;                                   // the update clips the gradient norm (StepMixin::clip_max > 0; the value is device data)
     void destroy() {
         for (auto x : exec) if (x) hipGraphExecDestroy(x);
@@ -329,6 +330,7 @@ struct StepMixin {
     int begin_backward_pass(float* G, hipStream_t st) {
         if (in_step) return MB_OK;           // the single-call step decided already (and replays a graph captured for that decision)
         stamp_live = word_zero = false;      // a backward nobody stamped
+        frz_dirty = true;                    // ... that computes every gradient, the frozen segments' too
         ow_pass = grads_zero && ow_enable;
         grads_zero = false;
         if (!(ow_pass && ow_covers)) CK(materialize_grads(G, st));      // this pass adds onto the range: it needs the zeros
@@ -386,6 +388,7 @@ struct StepMixin {
         struct Scope { StepMixin* m; ~Scope() { m->dyn = false; m->capturing = false; m->in_step = false; m->stage_mode = false; } } scope{this};
         dyn = true; in_step = true; stage_mode = true;
         stamp_live = word_zero = false;      // (the stage-driven step's prologue stamps nothing)
+        frz_dirty = true;                    // (and its backward ignores the frozen marks)
         if (mode == 2) return enqueue(st);
         StageGraph* g = nullptr;
         for (auto& x : stage_graphs)
@@ -428,11 +431,24 @@ struct StepMixin {
     // halves for that: slot c is class c as handed over, slot MB_CLASSES_MAX + c the same scalars with weight_decay = 0 (the prologue
     // writes both from the one cls[c]); riders and sweep pieces of a marked segment read the upper slot, so no kernel looks at a mark.
     // The marks are part of the map's identity (map_version), and set_update_map clears them.
+    // Frozen marks (mb_*_set_update_frozen): seg_frozen[s] != 0 -- no parameter group holds segment s.  Its parameters, shadow and moments
+    // are never touched: the sweep emits no update piece for it and no rider slice reaches into it.  A single-call step (in_step &&
+    // !stage_mode) also leaves out the launches whose whole output is frozen (the engines: a layer's grouped weight gradient, the word
+    // scatter, MAG-BERT's embedding backward) and tells the mixin which ranges it therefore did not write (frz_unwritten); every other
+    // frozen range was written by a fused kernel and gets a clear-only piece (kernels.h MB_PIECE_CLEAR) in the step's ONE sweep.
+    // The explicit and the stage-driven passes ignore the marks and compute every gradient.  Invariant behind the skipped launches:
+    // while marks are installed, the frozen ranges of G hold zeros whenever a single-call step begins -- frz_dirty says somebody
+    // (an explicit backward, torch, a step from before the marks) may have written there, and train_step_impl clears them once,
+    // outside any capture.  Like the no-decay marks they are part of map_version, and set_update_map clears them.
     struct ClassVals { float lr, beta1, beta2, eps, weight_decay; int correct_bias; };
     int n_classes = 0, map_version = 0;
     std::vector<size_t> seg_bounds;
     std::vector<int> seg_class;
-    std::vector<uint8_t> seg_nodecay;
+    std::vector<uint8_t> seg_nodecay, seg_frozen;
+    bool any_frozen = false, frz_dirty = true;
+    std::vector<std::pair<size_t, size_t>> frz_unwritten;       // frozen ranges the step being enqueued does not write (ascending, disjoint)
+    size_t ride_hopped = 0;                                     // frozen elements the rider cursor of the step being enqueued passed over
+    size_t frz_elems = 0; int frz_wgrad_skipped = 0, frz_embed_skipped = 0;       // the last enqueued single-call step (mb_*_freeze_stats)
     std::vector<ClassVals> class_vals;
     AdamArgs* class_table = nullptr;
     size_t upd_ridden = 0, upd_swept = 0; int upd_segments = 0;       // the last enqueued update (mb_*_update_stats)
@@ -481,14 +497,24 @@ struct StepMixin {
     }
     // the two launches between the backward and the sweep of a clipping step: every gradient of G[0, n) is final
     int enqueue_clip(const float* G, size_t n, char* ws, hipStream_t st) {
+        unsigned blocks = grad_norm_blocks(n);
+        if (any_frozen) {
+            // frozen segments: the norm of the trainable ranges only (their frozen neighbours hold what fused kernels wrote this step);
+            // never more blocks than the full range has, so the partials fit where ensure_clip_buf put them
+            AdamPieces tr;
+            CK(sweep_pieces(tr, 0, n, n, n, false));
+            CK(grad_sumsq_pieces(G, tr, clip_partials(), &blocks, st));
+        } else
         CK(grad_sumsq(G, n, clip_partials(), st));
         // (both halves of the class table: slots [n_classes, MB_CLASSES_MAX) in between hold nothing anybody reads)
         ClipTables t = {{adam_state(ws), n_classes > 0 ? class_state(ws) : nullptr}, {2, n_classes > 0 ? MB_CLASSES_MAX + n_classes : 0}};
-        return grad_clip_finalize(clip_partials(), grad_norm_blocks(n), clip_params(), 0.f, 1.f, clip_record(), t, st);
+        return grad_clip_finalize(clip_partials(), blocks, clip_params(), 0.f, 1.f, clip_record(), t, st);
     }
     int set_update_map(const std::vector<TensorInfo>& tensors, size_t n_update_end, int nc, int ns, const size_t* bounds, const int* classes) {
         if (nc == 0) {          // back to the two parameter groups (graphs captured for them were never dropped)
             n_classes = 0; seg_bounds.clear(); seg_class.clear(); seg_nodecay.clear(); class_vals.clear();
+            if (any_frozen) marks_changed();
+            seg_frozen.clear(); any_frozen = false;
             return MB_OK;
         }
         if (nc < 0 || nc > MB_CLASSES_MAX || ns < 1 || ns > MB_SEGMENTS_MAX || !bounds || !classes) return MB_ERR_ARG;
@@ -502,11 +528,13 @@ struct StepMixin {
         }
         const bool same = nc == n_classes && (int)seg_class.size() == ns && std::equal(classes, classes + ns, seg_class.begin()) &&
                           std::equal(bounds, bounds + ns + 1, seg_bounds.begin());
-        const bool marked = std::any_of(seg_nodecay.begin(), seg_nodecay.end(), [](uint8_t x) { return x != 0; });
+        const bool marked = any_frozen || std::any_of(seg_nodecay.begin(), seg_nodecay.end(), [](uint8_t x) { return x != 0; });
         if (same && !marked) return MB_OK;
+        if (any_frozen) marks_changed();
         if (!same) class_vals.clear();
         n_classes = nc; seg_bounds.assign(bounds, bounds + ns + 1); seg_class.assign(classes, classes + ns);
         seg_nodecay.assign((size_t)ns, 0);          // a map starts without marks: every segment decays as its class says
+        seg_frozen.assign((size_t)ns, 0); any_frozen = false;
         if (++map_version <= 0) map_version = 1;
         return MB_OK;
     }
@@ -518,6 +546,58 @@ struct StepMixin {
         if (same) return MB_OK;
         for (int s = 0; s < ns; ++s) seg_nodecay[s] = no_decay[s] ? 1 : 0;
         if (++map_version <= 0) map_version = 1;
+        return MB_OK;
+    }
+    // a change of frozen marks: what used to be frozen may hold anything a fused kernel wrote, what becomes frozen may hold a gradient --
+    // the next single-call step clears the frozen ranges first; and the word-row stamps prove nothing about a table that was left out
+    void marks_changed() { frz_dirty = true; stamp_live = word_zero = false; }
+    int set_update_frozen(int ns, const uint8_t* frozen) {
+        if (n_classes == 0) return MB_ERR_MODE;          // marks belong to a map
+        if (ns != (int)seg_class.size() || !frozen) return MB_ERR_ARG;
+        bool same = true;
+        for (int s = 0; s < ns; ++s) same = same && (frozen[s] != 0) == (seg_frozen[s] != 0);
+        if (same) return MB_OK;
+        any_frozen = false;
+        for (int s = 0; s < ns; ++s) { seg_frozen[s] = frozen[s] ? 1 : 0; any_frozen = any_frozen || frozen[s]; }
+        marks_changed();
+        if (++map_version <= 0) map_version = 1;
+        return MB_OK;
+    }
+    int freeze_stats(size_t* frozen_elems, int* wgrad_launches_skipped, int* embed_skipped) const {
+        if (frozen_elems) *frozen_elems = frz_elems;
+        if (wgrad_launches_skipped) *wgrad_launches_skipped = frz_wgrad_skipped;
+        if (embed_skipped) *embed_skipped = frz_embed_skipped;
+        return MB_OK;
+    }
+    size_t frozen_total() const {
+        size_t n = 0;
+        for (size_t s = 0; s + 1 < seg_bounds.size(); ++s) if (seg_frozen[s]) n += seg_bounds[s + 1] - seg_bounds[s];
+        return n;
+    }
+    // every element of [b, e) lies in a frozen segment
+    bool range_frozen(size_t b, size_t e) const {
+        if (!any_frozen || e <= b || seg_bounds.empty() || e > seg_bounds.back()) return false;
+        size_t s = (size_t)(std::upper_bound(seg_bounds.begin(), seg_bounds.end(), b) - seg_bounds.begin()) - 1;
+        for (; s + 1 < seg_bounds.size() && seg_bounds[s] < e; ++s) if (!seg_frozen[s]) return false;
+        return true;
+    }
+    // the launches this step may leave out: a single-call step under frozen marks (the explicit and stage-driven passes compute everything)
+    bool skipping() const { return any_frozen && in_step && !stage_mode; }
+    bool unwritten(size_t b, size_t e) const {
+        for (const auto& u : frz_unwritten) if (u.first <= b && e <= u.second) return true;
+        return false;
+    }
+    void note_unwritten(size_t b, size_t e) {
+        if (e <= b) return;
+        if (!frz_unwritten.empty() && frz_unwritten.back().second == b) frz_unwritten.back().second = e;
+        else frz_unwritten.push_back({b, e});
+        std::sort(frz_unwritten.begin(), frz_unwritten.end());
+    }
+    // zeros over the frozen ranges of G (never inside a capture: train_step_impl, before the prologue)
+    int clear_frozen(float* G, hipStream_t st) {
+        for (size_t s = 0; s + 1 < seg_bounds.size(); ++s)
+            if (seg_frozen[s]) CK(zero_fill(G + seg_bounds[s], (seg_bounds[s + 1] - seg_bounds[s]) * sizeof(float), st));
+        frz_dirty = false;
         return MB_OK;
     }
     // the slot of the device class table segment s reads: its class, or the class's weight_decay = 0 twin when the segment is marked
@@ -537,25 +617,67 @@ struct StepMixin {
     }
     // riders of a classed step: a slice that ends at element `top` (exclusive) may reach down to the start of the segment that holds
     // top - 1, and reads that segment's slot of the class table
-    void ride_segment(size_t top, size_t* floor, int* cls) const {
-        const size_t s = (size_t)(std::upper_bound(seg_bounds.begin(), seg_bounds.end(), top - 1) - seg_bounds.begin()) - 1;
-        *floor = seg_bounds[s]; *cls = seg_slot(s);
+    // A frozen segment under the cursor: when the step does not write it (frz_unwritten) the cursor hops over it, down to `limit` at
+    // most (what is final for this host), and the elements count as frozen, not ridden; otherwise the ride ends here -- the sweep owes
+    // that range a clear-only piece.  False: nothing to take.
+    bool ride_segment(size_t& cursor, size_t limit, size_t* floor, int* cls) {
+        while (cursor > limit) {
+            const size_t s = (size_t)(std::upper_bound(seg_bounds.begin(), seg_bounds.end(), cursor - 1) - seg_bounds.begin()) - 1;
+            if (!seg_frozen[s]) { *floor = seg_bounds[s]; *cls = seg_slot(s); return true; }
+            const size_t lo = std::max(seg_bounds[s], limit);
+            if (!unwritten(lo, cursor)) return false;
+            ride_hopped += cursor - lo; cursor = lo;
+        }
+        return false;
     }
     // the sweep of a classed step: [b0, e0) and [b1, e1) (ascending, disjoint) cut at the segment boundaries
-    int sweep_pieces(AdamPieces& out, size_t b0, size_t e0, size_t b1, size_t e1) const {
+    // A frozen segment gets no update piece.  clear: what the step's backward wrote of it (everything but frz_unwritten and the keep range
+    // [keep_b, keep_e), which stays "logically zero, physically stale" like its trainable neighbours) gets clear-only pieces, which lie
+    // behind every update piece of the table (kernels.h AdamPieces::clear_first).
+    int sweep_pieces(AdamPieces& out, size_t b0, size_t e0, size_t b1, size_t e1, bool clear = true, size_t keep_b = 0, size_t keep_e = 0) const {
         out = AdamPieces{};
         const size_t rb[2] = {b0, b1}, re[2] = {e0, e1};
-        size_t total4 = 0;
+        struct Piece { size_t lo, hi; int slot; };
+        std::vector<Piece> upd, clr;
         for (int r = 0; r < 2; ++r)
             for (size_t s = 0; s + 1 < seg_bounds.size(); ++s) {
                 const size_t lo = std::max(rb[r], seg_bounds[s]), hi = std::min(re[r], seg_bounds[s + 1]);
                 if (lo >= hi) continue;
-                if (out.count >= MB_SWEEP_PIECES_MAX) return MB_ERR_ARG;
-                if ((lo | hi) % 4 || hi / 4 > 0xffffffffull || total4 + (hi - lo) / 4 > 0xffffffffull) return MB_ERR_SHAPE;
-                out.begin4[out.count] = (uint32_t)(lo / 4); out.start4[out.count] = (uint32_t)total4; out.slot[out.count] = (uint8_t)seg_slot(s);
-                total4 += (hi - lo) / 4;
-                out.start4[++out.count] = (uint32_t)total4;
+                if (seg_frozen.empty() || !seg_frozen[s]) { upd.push_back({lo, hi, seg_slot(s)}); continue; }
+                if (!clear) continue;
+                // [lo, hi) minus the ranges nobody wrote
+                std::vector<std::pair<size_t, size_t>> holes = frz_unwritten;
+                if (keep_e > keep_b) holes.push_back({keep_b, keep_e});
+                std::sort(holes.begin(), holes.end());
+                size_t at = lo;
+                for (const auto& h : holes) {
+                    if (h.second <= at || h.first >= hi) continue;
+                    if (h.first > at) clr.push_back({at, h.first, MB_PIECE_CLEAR});
+                    at = std::max(at, std::min(h.second, hi));
+                }
+                if (at < hi) clr.push_back({at, hi, MB_PIECE_CLEAR});
             }
+        // (holes that do not fit the table: the two clear pieces -- ascending, disjoint -- with the smallest gap between them become one;
+        //  zeros over zeros, or, in the keep range, over values nobody reads)
+        while (upd.size() + clr.size() > (size_t)MB_SWEEP_PIECES_MAX && clr.size() > 1) {
+            size_t best = 1;
+            for (size_t k = 2; k < clr.size(); ++k)
+                if (clr[k].lo - clr[k - 1].hi < clr[best].lo - clr[best - 1].hi) best = k;
+            clr[best - 1].hi = clr[best].hi;
+            clr.erase(clr.begin() + (long)best);
+        }
+        if (upd.size() + clr.size() > (size_t)MB_SWEEP_PIECES_MAX) return MB_ERR_ARG;
+        size_t total4 = 0;
+        auto emit = [&](const Piece& pc) {
+            if ((pc.lo | pc.hi) % 4 || pc.hi / 4 > 0xffffffffull || total4 + (pc.hi - pc.lo) / 4 > 0xffffffffull) return (int)MB_ERR_SHAPE;
+            out.begin4[out.count] = (uint32_t)(pc.lo / 4); out.start4[out.count] = (uint32_t)total4; out.slot[out.count] = (uint8_t)pc.slot;
+            total4 += (pc.hi - pc.lo) / 4;
+            out.start4[++out.count] = (uint32_t)total4;
+            return (int)MB_OK;
+        };
+        for (const Piece& pc : upd) CK(emit(pc));
+        out.clear_first = out.count;
+        for (const Piece& pc : clr) CK(emit(pc));
         return MB_OK;
     }
     uint32_t* key_state(char* ws) const { return (uint32_t*)(ws + ws_state + 2 * sizeof(AdamArgs)); }
@@ -602,7 +724,12 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (m && e->n_classes > 0 && (int)e->class_vals.size() != e->n_classes) return MB_ERR_ARG;      // a map without this step's values
     // (a micro-step without the optimizer enqueues the same kernels under any map; data-parallel variants are positive, and refuse a map)
     if (m && e->n_classes > 0 && variant == 0) variant = -e->map_version;
+    // (... except under frozen marks: every single-call step then leaves launches out, the micro-steps of an accumulation window too)
+    if (e->any_frozen && variant > 0) return MB_ERR_MODE;
+    if (e->any_frozen && variant == 0) variant = -e->map_version;
     e->upd_ridden = e->upd_swept = 0; e->upd_segments = 0;
+    e->frz_elems = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
+    if (e->any_frozen && e->frz_dirty) CK(e->clear_frozen(e->G, st));
     if (m && e->n_classes > 0) CK(e->ensure_class_table());
     const bool clip = m && e->clip_max > 0.f;
     if (clip && variant > 0) return MB_ERR_MODE;          // (the data-parallel steps refuse before they get here)
@@ -632,7 +759,10 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     } flags{e, false, m != nullptr, stale_before};
     // untouched word rows (StepMixin::stamp_live): this step's prologue stamps its batch, so a window that is live stays live, and
     // word gradients the engine itself left all zero open one
-    const bool stamping = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable && ids != nullptr;
+    // (frozen marks: a step without an embedding backward has nobody to consume -- and clear -- the count table, and no sweep piece over
+    //  the word table for stamps to guide)
+    const bool no_embed = e->any_frozen && e->embed_all_frozen();
+    const bool stamping = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable && ids != nullptr && !no_embed;
     if (!stamping) e->stamp_live = false;
     else if (e->word_zero) e->stamp_live = true;
     e->word_zero = false;                   // (this step's backward writes some of them)
@@ -647,7 +777,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     e->packed_w = pa.magw.W_hv != nullptr;
     pa.seed = seed; pa.step = step; pa.keys = e->key_state(ws); pa.nsites = e->nsites;
     pa.zero_dw = (uint32_t*)loss; e->loss_cleared = loss != nullptr;
-    if (e->idcnt_enable && ids) { pa.ids = (const int64_t*)ids; pa.n_ids = B * L; pa.id_count = (int*)(ws + e->idcnt_off); }
+    if (e->idcnt_enable && ids && !no_embed) { pa.ids = (const int64_t*)ids; pa.n_ids = B * L; pa.id_count = (int*)(ws + e->idcnt_off); }
     e->counted = pa.id_count != nullptr;
     if (stamping) { pa.stamp = e->stamp_table(ws); pa.stamp_state = e->stamp_state(ws); pa.stamp_no = e->sweep_no; pa.stamp_on = e->stamp_live ? 1u : 0u; }
     if (m) {
@@ -714,6 +844,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
             ng.graph.push_back(gr); ng.exec.push_back(ex);
         }
         ng.ridden = e->upd_ridden; ng.swept = e->upd_swept; ng.segments = e->upd_segments;
+        ng.frozen = e->frz_elems; ng.wgrad_skipped = e->frz_wgrad_skipped; ng.embed_skipped = e->frz_embed_skipped;
         e->graphs.push_back(ng);
         g = &e->graphs.back();
         ++e->graph_captures;
@@ -724,6 +855,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     }
     ++e->graph_launches;
     e->upd_ridden = g->ridden; e->upd_swept = g->swept; e->upd_segments = g->segments;
+    e->frz_elems = g->frozen; e->frz_wgrad_skipped = g->wgrad_skipped; e->frz_embed_skipped = g->embed_skipped;
     flags.ok = true;
     return MB_OK;
 }

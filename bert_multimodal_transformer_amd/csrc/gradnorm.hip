@@ -56,6 +56,40 @@ __global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict
     if (threadIdx.x == 0) partial[blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
 }
 
+// The sum over a table of pieces (kernels.h AdamPieces: quads [begin4[k], begin4[k] + start4[k + 1] - start4[k]) of g): the pieces laid end
+// to end are cut into one contiguous share per block, a block walks the pieces its share overlaps in table order.  Every address is a
+// whole quad (the pieces are tensor-aligned offsets into a 16-byte aligned buffer).
+__global__ void __launch_bounds__(256) grad_sumsq_pieces_kernel(const float* __restrict__ g, const AdamPieces R, double* __restrict__ partial) {
+    const size_t total4 = R.start4[R.count];
+    const size_t per = ((total4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const size_t vb = (size_t)blockIdx.x * per, ve = min(total4, vb + per);
+    const f32x4* __restrict__ q = (const f32x4*)g;
+    double acc[2] = {0.0, 0.0};
+#pragma unroll 1
+    for (int k = 0; k < R.count; ++k) {
+        const size_t off = R.start4[k], nxt = R.start4[k + 1];
+        if (nxt <= vb) continue;
+        if (off >= ve) break;
+        const size_t lo = max(vb, off), hi = min(ve, nxt);
+        if (lo >= hi) continue;
+        const size_t base4 = (size_t)R.begin4[k] - off;
+        size_t i = base4 + lo + threadIdx.x;
+        const size_t end = base4 + hi;
+        for (; i + 256 < end; i += 512) {
+            const f32x4 x0 = q[i], x1 = q[i + 256];
+            acc[0] = sq4(x0, acc[0]); acc[1] = sq4(x1, acc[1]);
+        }
+        if (i < end) acc[0] = sq4(q[i], acc[0]);
+    }
+    double s = acc[0] + acc[1];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    __shared__ double wave_sum[4];
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
 // One block.  The partials are summed in index order in two levels: thread t adds partials [8t, 8t + 8) one after the other, thread 0 then
 // adds the 256 sums one after the other.  dyn (device, may be null): {max_norm, grad_scale} of this step, where the step prologue put them.
 __global__ void __launch_bounds__(256) grad_clip_finalize_kernel(const double* __restrict__ partial, unsigned blocks, const float* __restrict__ dyn,
@@ -90,6 +124,16 @@ __global__ void __launch_bounds__(256) grad_clip_finalize_kernel(const double* _
 int grad_sumsq(const float* g, size_t n, double* partial, hipStream_t st) {
     if ((n && !g) || !partial || ((uintptr_t)g & 3) || ((uintptr_t)partial & 7)) return MB_ERR_ARG;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(grad_norm_blocks(n)), dim3(256), 0, st, g, n, partial);
+    return (int)hipGetLastError();
+}
+
+int grad_sumsq_pieces(const float* g, const AdamPieces& r, double* partial, unsigned* blocks, hipStream_t st) {
+    if (!g || !partial || !blocks || ((uintptr_t)g & 15) || ((uintptr_t)partial & 7)) return MB_ERR_ARG;
+    if (r.count < 0 || r.count > MB_SWEEP_PIECES_MAX || (r.count && r.start4[0] != 0u)) return MB_ERR_ARG;
+    for (int k = 0; k < r.count; ++k) if (r.start4[k + 1] < r.start4[k]) return MB_ERR_SHAPE;
+    const size_t n4 = r.count ? r.start4[r.count] : 0;
+    *blocks = grad_norm_blocks(n4 * 4);          // (no piece at all: one block that writes a zero)
+    hipLaunchKernelGGL(grad_sumsq_pieces_kernel, dim3(*blocks), dim3(256), 0, st, g, r, partial);
     return (int)hipGetLastError();
 }
 

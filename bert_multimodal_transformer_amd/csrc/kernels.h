@@ -314,7 +314,12 @@ int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const Adam
 #define MB_CLASSES_MAX 32
 #define MB_SEGMENTS_MAX 128
 #define MB_SWEEP_PIECES_MAX (MB_SEGMENTS_MAX + 2)
-struct AdamPieces { uint32_t begin4[MB_SWEEP_PIECES_MAX], start4[MB_SWEEP_PIECES_MAX + 1]; uint8_t slot[MB_SWEEP_PIECES_MAX]; int count; };
+// Clear-only pieces (frozen segments, mb_*_set_update_frozen): slot == MB_PIECE_CLEAR -- the piece's gradient range gets zeros and no
+// parameter, moment or shadow byte of it is read or written; what a backward still wrote into a range no parameter group holds.
+// They lie behind every update piece of the table: pieces [0, clear_first) update, pieces [clear_first, count) clear (start4 runs on
+// through both), and extra blocks of the same launch take them.
+#define MB_PIECE_CLEAR 0xff
+struct AdamPieces { uint32_t begin4[MB_SWEEP_PIECES_MAX], start4[MB_SWEEP_PIECES_MAX + 1]; uint8_t slot[MB_SWEEP_PIECES_MAX]; int count, clear_first; };
 int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
                         size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st);
 
@@ -327,6 +332,10 @@ int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, co
 // pointer, may be null): {max_norm, grad_scale} are read from there instead (replayed step graphs: PrologueArgs::clip).
 unsigned grad_norm_blocks(size_t n);
 int grad_sumsq(const float* g, size_t n, double* partial, hipStream_t st);
+// grad_sumsq_pieces: the same sum over the pieces of `r` only (begin4 / start4 as the classed sweep reads them, slots ignored): a step that
+// freezes segments takes the norm of the trainable ranges.  The pieces laid end to end are cut into one contiguous share per block on the
+// host's layout alone (blocks = grad_norm_blocks(4 * start4[count])), every block adds its share in index order: the same bits on every run.
+int grad_sumsq_pieces(const float* g, const AdamPieces& r, double* partial, unsigned* blocks, hipStream_t st);
 struct ClipTables { AdamArgs* tab[2]; int count[2]; };
 int grad_clip_finalize(const double* partial, unsigned blocks, const float* dyn, float max_norm, float grad_scale, float* out2,
                        const ClipTables& t, hipStream_t st);

@@ -28,6 +28,8 @@ struct mb_xlnet_engine : StepMixin {
     size_t mag_whv, mag_wha, mag_wv, mag_wa, mag_bhv, mag_bha, mag_bv, mag_ba, mag_lnw, mag_lnb;
     size_t n_params, n_trainable, n_decay, sh_begin, sh_end;
     size_t n_update_end() const { return n_trainable; }       // (StepMixin: the range an update covers, and its clipping norm)
+    size_t layer_end(int l) const { return l + 1 < c.n_layer ? lo[l + 1].q : wsum; }      // (a layer's seven GEMM weights are contiguous)
+    bool embed_all_frozen() const { return false; }           // (StepMixin: MAG-XLNet counts no token ids; its scatter is left out by the word table alone)
     // (dp_step.h: the layers' GEMM weights are [layer_begin(0), layers_end()) of the decay slab, layer by layer)
     int n_layers() const { return c.n_layer; }
     size_t layer_begin(int l) const { return lo[l].q; }
@@ -282,6 +284,7 @@ int mb_xlnet_bind(mb_xlnet_engine* e, float* params, float* grads, void* shadow,
     if (e->c.dtype == DT_BF16 && !shadow) return MB_ERR_ARG;
     e->P = params; e->G = grads; e->SH = (char*)shadow; e->ws = (char*)workspace;
     e->grads_zero = false;                 // a newly bound gradient buffer: nothing is known about its contents
+    e->frz_dirty = true;
     e->ws_zeroed = false; e->padT = -1;
     e->drop_graphs();
     char* mws = e->ws + e->ws_mag;
@@ -423,7 +426,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
         const AdamArgs* dyn = e->adam_state(ws);
         if (e->n_classes > 0) {
             size_t sb = 0; int cl = 0;
-            e->ride_segment(e->ride_cursor, &sb, &cl);
+            if (!e->ride_segment(e->ride_cursor, floor, &sb, &cl)) return r;          // (hops over frozen layers; false: nothing left for this host)
             floor = std::max(floor, sb); dyn = e->class_state(ws) + cl;
         }
         const size_t take = std::min(e->ride_cursor - floor, budget) / 1024 * 1024;
@@ -489,16 +492,19 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
             int wtile = e->group_wgrad;
             if (wtile == 256 && !gemm_grouped_tn_ok(dt, wg, nwg, 256)) wtile = 128;      // (a short k range in the group: the 128 x 128 kernel)
             const bool grouped = wtile > 0 && gemm_grouped_tn_ok(dt, wg, nwg, wtile);
+            // frozen marks: a single-call step leaves out the weight gradients of a layer whose seven GEMM weights nobody updates (as engine.hip)
+            const bool wfrozen = e->skipping() && e->unwritten(o.q, e->layer_end(l));
+            if (wfrozen) ++e->frz_wgrad_skipped;
             if (grouped) {
                 for (GemmArgs& a : wg) a.overwrite = e->ow_pass ? 1 : 0;
                 wg[7].overwrite = 1;
             }
-            if (!grouped) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, H, I, Tk, dzdA, H, ws + w.g, I, G + o.w2, I, st));
             const bool riding = grouped && e->ride_m != nullptr;
             auto take_l = [&](size_t budget, int blocks) { return take_ride(l, budget, blocks); };
             CK(dgrad_with_riders(dt, EPI_DGELU, T, I, H, dzdA, H, e->W(o.w2), I, du, I, ws + w.u, I, G + o.b1, e->key(XS_LAYER0 + 8 * l + 2, pd), acc, st,
                                  riding, e->ride_opts, e->cu_count(), take_l));
-            if (!grouped) CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, I, H, Tk, du, I, ws + w.y1, H, G + o.w1, H, st));
             CK(dgrad_with_riders(dt, EPI_ADD_RES, T, H, I, du, I, e->W(o.w1), H, t1, H, dsA, H, nullptr, kNoDrop, GradAcc{}, st, riding, e->ride_opts,
                                  e->cu_count(), take_l));
             // ---- relative attention block
@@ -523,7 +529,7 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                 CK(ln_reduce_partials_layers((const float*)(ws + e->ws_lnp_a), (const float*)(ws + e->ws_lnp_b), e->lnp_stride,
                                              mag_slabs ? NL + 1 : NL, nblk, H, dst, st, acc));
             }
-            if (!grouped) CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.vec, H, G + o.o, H, st));
+            if (!grouped && !wfrozen) CK(wgrad(dt, H, H, Tk, dzdB, H, ws + w.vec, H, G + o.o, H, st));
             CK(dgrad_with_riders(dt, EPI_ADD_RES, T, H, H, dzdB, H, e->W(o.o), H, ws + e->ws_dvec, H, nullptr, 0, nullptr, kNoDrop, GradAcc{}, st, riding,
                                  e->ride_opts, e->cu_count(), take_l));
             // (riders of the two relative-attention backward launches: 576 workgroups in 768 slots each at L = 50, latency-bound hosts)
@@ -550,10 +556,10 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                                         rkv.blocks ? &rkv : nullptr, ws + w.vec, e->attn_stats(w), e->attn_pdsave(), e->perm));
             if (grouped) {
                 CK(e->prof_mark(2 * l, st));
-                CK(gemm_grouped_tn_launch(dt, wg, nwg, wtile, st));
+                if (!wfrozen) CK(gemm_grouped_tn_launch(dt, wg, nwg, wtile, st));
                 CK(e->prof_mark(2 * l + 1, st));
-                if (nwg == 8) CK(add_f32(G + o.r, (const float*)(ws + e->ws_rhalf), (size_t)H * H, st));
-            } else {
+                if (nwg == 8 && !wfrozen) CK(add_f32(G + o.r, (const float*)(ws + e->ws_rhalf), (size_t)H * H, st));
+            } else if (!wfrozen) {
                 CK(wgrad(dt, H, H, Rk, ws + e->ws_pos, H, dkr, H, G + o.r, H, st));        // (one by one: the whole K range, no scratch)
                 CK(wgrad(dt, H, H, Tk, xin, H, dqkv, 3 * H, G + o.q, H, st));
                 CK(wgrad(dt, H, H, Tk, xin, H, dqkv + (size_t)H * es, 3 * H, G + o.k, H, st));
@@ -600,6 +606,9 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
                 }
             }
         } else {
+            // (frozen marks, single-call step: no scatter into a word table nobody updates -- the launch has no other output)
+            if (e->skipping() && e->ids && e->unwritten(e->word, e->word + (size_t)c.vocab_size * H)) e->frz_embed_skipped = 1;
+            else
             CK(gather_drop_backward(dt, ws + e->ws_dxa, e->ids, e->ids ? G + e->word : (float*)(ws + e->ws_demb), T, H, e->key(XS_EMB, pd), st, acc));
             // deterministic mode: the integer sums become part of the fp32 gradients before anybody (AdamW, an exchange) reads them
             CK(grad_fold(acc, G, e->det_begin, e->det_end, st));
@@ -624,20 +633,28 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
                       !e->prof && !e->mems && !clip;
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wsum;
+    // frozen marks: what this step's backward will not write (StepMixin::frz_unwritten): the GEMM weights of fully frozen layers, a frozen word table
+    e->frz_unwritten.clear(); e->ride_hopped = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
+    e->frz_elems = e->any_frozen ? e->frozen_total() : 0;
+    if (e->skipping()) {
+        for (int l = 0; l < e->c.n_layer; ++l) if (e->range_frozen(e->lo[l].q, e->layer_end(l))) e->note_unwritten(e->lo[l].q, e->layer_end(l));
+        const size_t word_end = e->word + (size_t)e->c.vocab_size * e->c.d_model;
+        if (e->range_frozen(e->word, word_end)) e->note_unwritten(e->word, word_end);
+    }
     const int rb = mb_xlnet_backward(e, nullptr, lab, loss_scale, 0, e->c.n_layer + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
     if (clip) CK(e->enqueue_clip(e->G, e->n_trainable, ws, st));      // the whole gradient is final: its norm, the coefficient into the sweep's scalars
     if (m && v) {
-        e->upd_ridden = ride ? e->wsum - e->ride_cursor : 0; e->upd_swept = e->n_trainable - e->upd_ridden;
+        e->upd_ridden = ride ? e->wsum - e->ride_cursor - e->ride_hopped : 0; e->upd_swept = e->n_trainable - e->upd_ridden - e->frz_elems;
         e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
     }
     if (m && v && e->n_classes > 0) {
         // Classed step (kernels.h AdamPieces): what the riders left and the rest of both slabs, cut at the segment boundaries, every piece
         // with its class's slot, as ONE launch
         AdamPieces pieces;
-        CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wsum, e->wsum, e->n_trainable));
         const bool keep = e->keep_in_step();
+        CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wsum, e->wsum, e->n_trainable, true, keep ? e->stale_begin : 0, keep ? e->stale_end : 0));
         CK(e->prof_mark(2 * e->c.n_layer, st));
         CK(adamw_sweep_classed(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, pieces, e->sh_begin, e->sh_end,
                                keep ? e->stale_begin : 0, keep ? e->stale_end : 0, e->class_state(ws), WordSkip{}, st));
@@ -676,6 +693,14 @@ int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* l
                                const float* weight_decay, const int* correct_bias) {
     if (!e) return MB_ERR_ARG;
     return e->set_update_values(n_classes, lr, beta1, beta2, eps, weight_decay, correct_bias);
+}
+int mb_xlnet_set_update_frozen(mb_xlnet_engine* e, int n_segments, const uint8_t* frozen) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_update_frozen(n_segments, frozen);
+}
+int mb_xlnet_freeze_stats(const mb_xlnet_engine* e, size_t* frozen_elems, int* wgrad_launches_skipped, int* embed_skipped) {
+    if (!e) return MB_ERR_ARG;
+    return e->freeze_stats(frozen_elems, wgrad_launches_skipped, embed_skipped);
 }
 int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments) {
     if (!e) return MB_ERR_ARG;
@@ -779,6 +804,7 @@ int mb_xlnet_mark_grads_zero(mb_xlnet_engine* e, int known_zero) {
     if (!e) return MB_ERR_ARG;
     e->grads_zero = known_zero != 0;
     if (known_zero) e->grads_stale = false;
+    else e->frz_dirty = true;          // somebody else is writing gradients, maybe into frozen segments
     return MB_OK;
 }
 

@@ -122,6 +122,12 @@ def get_parser():
     parser.add_argument("--max_grad_norm", type=float, default=0.0,
                         help="clip the global gradient norm to this value in front of every optimizer update, inside the single-call "
                              "step (AdamW(max_grad_norm=...)); 0 = off, the default: the reference does not clip")
+    parser.add_argument("--freeze_layers", type=int, default=0,
+                        help="freeze the lowest N encoder layers (model.freeze): they are in no parameter group, and the single-call "
+                             "step runs no weight-gradient launch for them; 0 = off")
+    parser.add_argument("--freeze_embeddings", type=str2bool, nargs="?", const=True, default=False,
+                        help="freeze the embedding tables (MAG-BERT: word, position, token-type and their LayerNorm; MAG-XLNet: the "
+                             "word table): no embedding backward, no update of the tables")
     return parser
 
 
@@ -379,13 +385,16 @@ def set_random_seed(seed: int):
 
 
 def optimizer_grouped_parameters(model, weight_decay=0.01):
-    """multimodal_driver.py:328-343."""
-    param_optimizer = list(model.named_parameters())
+    """multimodal_driver.py:328-343.  Parameters whose requires_grad is false (model.freeze) are in no group, and a group that
+    freezing emptied is left out; with nothing frozen: the reference's two groups."""
+    everything = list(model.named_parameters())
+    param_optimizer = [(n, p) for n, p in everything if p.requires_grad]
     no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
-    return [
+    groups = [
         {"params": [p for n, p in param_optimizer if not any(nd in n for nd in no_decay)], "weight_decay": weight_decay},
         {"params": [p for n, p in param_optimizer if any(nd in n for nd in no_decay)], "weight_decay": 0.0},
     ]
+    return groups if len(param_optimizer) == len(everything) else [g for g in groups if g["params"]]
 
 
 def prep_for_training(num_train_optimization_steps: int):
@@ -416,6 +425,9 @@ def prep_for_training(num_train_optimization_steps: int):
             model = MAG_XLNetForSequenceClassification(xlnet_config(args.model), multimodal_config, visual_dim=V,
                                                        acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     model.to(_device())
+    if args.freeze_layers > 0 or args.freeze_embeddings:
+        # the common fine-tuning recipe: the groups below leave the frozen parameters out, and the single-call step skips their work
+        model.freeze(embeddings=args.freeze_embeddings, layers=args.freeze_layers)
     if args.layer_lr_decay != 1.0 or args.head_learning_rate is not None:
         # per-group learning rates: still ONE engine call per optimizer step (update classes, optimization.AdamW.flat_step_args)
         n_layers = model.config.num_hidden_layers if args.model in BERT_MODELS else model.config.n_layer
@@ -591,6 +603,7 @@ def train(model, train_dataloader, validation_dataloader, test_data_loader, opti
         train_loss = train_epoch(model, train_dataloader, optimizer, scheduler)
         torch.cuda.synchronize()
         dt = time.time() - t0
+        frozen = model._core.freeze_stats() if (args.freeze_layers > 0 or args.freeze_embeddings) else None
         valid_loss = eval_epoch(model, validation_dataloader, optimizer)
         test_acc, test_mae, test_corr, test_f_score = test_score_model(model, test_data_loader)
         if _dist()[0] != 0:
@@ -598,6 +611,8 @@ def train(model, train_dataloader, validation_dataloader, test_data_loader, opti
         print("epoch:{}, train_loss:{}, valid_loss:{}, test_acc:{}".format(epoch_i, train_loss, valid_loss, test_acc))
         valid_losses.append(valid_loss)
         test_accuracies.append(test_acc)
+        if frozen is not None:       # what the last training step of the epoch left out (include/magbert_hip.h: mb_*_freeze_stats)
+            print(json.dumps({"frozen_params": frozen[0], "wgrad_launches_skipped": frozen[1], "embed_backward_skipped": frozen[2]}))
         print(json.dumps({k: float(v) for k, v in {
             "train_loss": train_loss, "valid_loss": valid_loss, "test_acc": test_acc, "test_mae": test_mae,
             "test_corr": test_corr, "test_f_score": test_f_score, "best_valid_loss": min(valid_losses),

@@ -27,7 +27,10 @@ UPDATE_CLASSES_MAX = 32
 UPDATE_SEGMENTS_MAX = 128
 
 
-def plan_update_segments(tensors, group_of_tensor, n_update_end):
+FROZEN = -1          # the class plan_*_segments(..., frozen=True) gives a segment no parameter group holds
+
+
+def plan_update_segments(tensors, group_of_tensor, n_update_end, frozen=False):
     """The segment map of a classed single-call step (include/magbert_hip.h: mb_*_set_update_map), from the flat layout alone.
 
     tensors: the layout's table, (name, offset, numel, ...) per tensor (_Core.tensors); group_of_tensor: per tensor the index of the
@@ -36,7 +39,12 @@ def plan_update_segments(tensors, group_of_tensor, n_update_end):
     boundaries[s + 1]) -- a maximal run of consecutive tensors of one group, the alignment gap behind a tensor included -- belongs to
     group classes[s]; boundaries are tensor offsets, from 0 to n_update_end.  None when a tensor below n_update_end is not in
     exactly one group, the tensors do not tile [0, n_update_end), or there are more than UPDATE_CLASSES_MAX groups or
-    UPDATE_SEGMENTS_MAX segments."""
+    UPDATE_SEGMENTS_MAX segments.
+
+    frozen=True: a tensor no group holds (None, or an empty collection) is frozen, not a reason to decline.  A maximal run of consecutive
+    frozen tensors is a segment of class FROZEN, and the result is (boundaries, classes, frozen_flags) with one 0 / 1 flag per segment
+    (include/magbert_hip.h: mb_*_set_update_frozen).  Frozen segments count towards UPDATE_SEGMENTS_MAX, FROZEN is no class; None when
+    every tensor is frozen."""
     if len(tensors) != len(group_of_tensor):
         return None
     rows = sorted((int(t[1]), int(t[2]), g) for t, g in zip(tensors, group_of_tensor) if int(t[1]) < n_update_end)
@@ -44,9 +52,13 @@ def plan_update_segments(tensors, group_of_tensor, n_update_end):
     cursor = 0
     for off, numel, g in rows:
         if isinstance(g, (list, tuple, set, frozenset)):
-            if len(g) != 1:
+            if len(g) > 1 or (len(g) == 0 and not frozen):
                 return None
-            g = next(iter(g))
+            g = next(iter(g)) if g else None
+        if g is None and frozen:
+            g = FROZEN
+        elif g is not None and frozen and int(g) < 0:
+            return None
         if g is None or off != cursor or numel < 1:
             return None
         cursor = (off + numel + 63) // 64 * 64          # tensors are 64-float aligned in the flat layout
@@ -56,8 +68,11 @@ def plan_update_segments(tensors, group_of_tensor, n_update_end):
     if cursor != n_update_end or not classes:
         return None
     boundaries.append(int(n_update_end))
-    if len(set(classes)) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
+    real = set(classes) - ({FROZEN} if frozen else set())
+    if not real or len(real) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
         return None
+    if frozen:
+        return boundaries, classes, [1 if c == FROZEN else 0 for c in classes]
     return boundaries, classes
 
 
@@ -103,11 +118,12 @@ def pair_update_groups(hyper, hints=None):
     return class_of, no_decay, members
 
 
-def plan_paired_segments(tensors, group_of_tensor, n_update_end, class_of_group, no_decay_of_group):
+def plan_paired_segments(tensors, group_of_tensor, n_update_end, class_of_group, no_decay_of_group, frozen=False):
     """plan_update_segments over the classes of paired groups (pair_update_groups): (boundaries, classes, no_decay_flags).  A segment
     is a maximal run of consecutive tensors of one class AND one flag -- the decayed and the undecayed tensors of a class that touch
     are two segments -- and flag s is 1 where segment s holds a zero-decay partner's tensors.  None under plan_update_segments' own
-    conditions, with the classes counted after pairing."""
+    conditions, with the classes counted after pairing.  frozen=True, as there: tensors no group holds become segments of class FROZEN
+    (no-decay flag 0), and the result is (boundaries, classes, no_decay_flags, frozen_flags)."""
     if len(tensors) != len(group_of_tensor):
         return None
     rows = sorted((int(t[1]), int(t[2]), g) for t, g in zip(tensors, group_of_tensor) if int(t[1]) < n_update_end)
@@ -115,13 +131,18 @@ def plan_paired_segments(tensors, group_of_tensor, n_update_end, class_of_group,
     cursor = 0
     for off, numel, g in rows:
         if isinstance(g, (list, tuple, set, frozenset)):
-            if len(g) != 1:
+            if len(g) > 1 or (len(g) == 0 and not frozen):
                 return None
-            g = next(iter(g))
-        if g is None or off != cursor or numel < 1 or not 0 <= int(g) < len(class_of_group):
+            g = next(iter(g)) if g else None
+        if off != cursor or numel < 1:
             return None
+        if g is None and frozen:
+            c, f = FROZEN, 0
+        elif g is None or not 0 <= int(g) < len(class_of_group):
+            return None
+        else:
+            c, f = int(class_of_group[int(g)]), 1 if no_decay_of_group[int(g)] else 0
         cursor = (off + numel + 63) // 64 * 64          # tensors are 64-float aligned in the flat layout
-        c, f = int(class_of_group[int(g)]), 1 if no_decay_of_group[int(g)] else 0
         if not classes or classes[-1] != c or flags[-1] != f:
             boundaries.append(off)
             classes.append(c)
@@ -129,8 +150,11 @@ def plan_paired_segments(tensors, group_of_tensor, n_update_end, class_of_group,
     if cursor != n_update_end or not classes:
         return None
     boundaries.append(int(n_update_end))
-    if len(set(classes)) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
+    real = set(classes) - ({FROZEN} if frozen else set())
+    if not real or len(real) > UPDATE_CLASSES_MAX or len(classes) > UPDATE_SEGMENTS_MAX:
         return None
+    if frozen:
+        return boundaries, classes, flags, [1 if c == FROZEN else 0 for c in classes]
     return boundaries, classes, flags
 
 
@@ -153,16 +177,20 @@ def layerwise_lr_groups(named_parameters, num_layers, lr, layer_decay=1.0, head_
     """Parameter groups for AdamW with layer-wise learning-rate decay and / or a learning rate of their own for the new parameters.
 
     named_parameters: (name, parameter) pairs.  Depth 0 = the embeddings, depth l + 1 = `encoder.layer.l.` (BERT) / `transformer.layer.l.`
-    (XLNet, its per-layer relative-attention biases included), any other encoder parameter goes with the embeddings; depth d trains at
+    (XLNet, its per-layer relative-attention biases included), any other encoder parameter goes with the embeddings; parameters whose
+    requires_grad is false (model.freeze) are in no group; depth d trains at
     lr * layer_decay ** (num_layers + 1 - d).  The new parameters -- MAG.*, the pooler, classifier, sequence_summary, logits_proj --
     train at head_lr (lr when None).  Every learning rate is split by the reference's no-decay rule (multimodal_driver.py:336: bias,
     LayerNorm.bias, LayerNorm.weight in the name); empty groups are dropped.  With layer_decay == 1.0 and head_lr None the result is
     exactly multimodal_driver.optimizer_grouped_parameters(): two groups without an lr of their own."""
-    named = list(named_parameters)
+    everything = list(named_parameters)
+    named = [(n, p) for n, p in everything if getattr(p, "requires_grad", True)]          # frozen parameters (model.freeze) are in no group
     is_nd = lambda n: any(nd in n for nd in _NO_DECAY)
     if layer_decay == 1.0 and head_lr is None:
-        return [{"params": [p for n, p in named if not is_nd(n)], "weight_decay": weight_decay},
-                {"params": [p for n, p in named if is_nd(n)], "weight_decay": 0.0}]
+        two = [{"params": [p for n, p in named if not is_nd(n)], "weight_decay": weight_decay},
+               {"params": [p for n, p in named if is_nd(n)], "weight_decay": 0.0}]
+        # (with nothing frozen: the two groups as ever, even an empty one; a group that freezing emptied is left out)
+        return two if len(named) == len(everything) else [g for g in two if g["params"]]
     buckets = {}
     for n, p in named:
         d = _depth_of(n, num_layers)
@@ -198,6 +226,7 @@ class AdamW(torch.optim.Optimizer):
         self._clip_last = None         # where the last update left (norm, coef): a core (single-call step) or the two floats
         self.fused_zero_grad = True    # clear gradients inside the update kernel (zero_grad() then costs nothing)
         self._plan = None
+        self._class_frozen = {}        # per flat buffer: the frozen flags of that map's segments (tensors no group holds), or None
         self._class_maps = {}          # per flat buffer: the segment map of a classed single-call step (flat_step_args), or None
         self._t = 0
         self._dp = None              # set by distributed.DataParallel
@@ -339,7 +368,8 @@ class AdamW(torch.optim.Optimizer):
         takes gets the map it always got, with no_decay = None.  Only when it declines are the groups paired (pair_update_groups,
         plan_paired_segments): classes then stand for up to two groups, groups[c] is the one whose values class c carries, partners[c]
         = (that group, its zero-decay partner or None), and no_decay marks the partner's segments.  The plan is computed once;
-        flat_step_args drops it when a pair no longer holds."""
+        flat_step_args drops it when a pair no longer holds.  Tensors no group holds are frozen: _class_frozen keeps one flag per
+        segment for them (1 = frozen; None when every tensor has a group)."""
         if id(core) not in self._class_maps:
             owner = {}
             for gi, group in enumerate(self.param_groups):
@@ -348,18 +378,23 @@ class AdamW(torch.optim.Optimizer):
                     if info is not None and info[0] is core:
                         owner.setdefault(info[1], set()).add(gi)
             n_end = getattr(core, "n_update_end", core.n_params)
-            planned = plan_update_segments(core.tensors, [owner.get(t[1]) for t in core.tensors], n_end)
+            # tensors no group holds are frozen (model.freeze + groups built from requires_grad): segments of their own, marked, whose
+            # class is not looked at (they carry class 0)
+            owners = [owner.get(t[1]) for t in core.tensors]
+            planned = plan_update_segments(core.tensors, owners, n_end, frozen=True)
             if planned is not None:
-                groups = sorted(set(planned[1]))
-                planned = (planned[0], [groups.index(g) for g in planned[1]], groups, None, [(g, None) for g in groups])
+                groups = sorted(set(planned[1]) - {FROZEN})
+                self._class_frozen[id(core)] = planned[2] if any(planned[2]) else None
+                planned = (planned[0], [0 if g == FROZEN else groups.index(g) for g in planned[1]], groups, None, [(g, None) for g in groups])
             else:
                 class_of, no_decay, members = pair_update_groups([self._hyper(g) for g in self.param_groups],
                                                                  hints=[g.get("initial_lr") for g in self.param_groups])
-                paired = plan_paired_segments(core.tensors, [owner.get(t[1]) for t in core.tensors], n_end, class_of, no_decay)
+                paired = plan_paired_segments(core.tensors, owners, n_end, class_of, no_decay, frozen=True)
                 if paired is not None:
-                    used = sorted(set(paired[1]))          # (groups without a tensor in this buffer leave holes in the class ids)
-                    planned = (paired[0], [used.index(c) for c in paired[1]], [members[c][0] for c in used], paired[2],
+                    used = sorted(set(paired[1]) - {FROZEN})          # (groups without a tensor in this buffer leave holes in the class ids)
+                    planned = (paired[0], [0 if c == FROZEN else used.index(c) for c in paired[1]], [members[c][0] for c in used], paired[2],
                                [members[c] for c in used])
+                    self._class_frozen[id(core)] = paired[3] if any(paired[3]) else None
             self._class_maps[id(core)] = planned
         return self._class_maps[id(core)]
 
@@ -374,7 +409,9 @@ class AdamW(torch.optim.Optimizer):
         pair's decaying group.  A cached pairing is checked on every call -- a pair whose groups no longer agree is planned again, which
         may end in None.  Either dictionary carries "max_grad_norm" (0.0 = no clipping), which the step installs
         with mb_*_set_grad_clip; under allow_dp a clipping optimizer gets None -- the data-parallel single call has no norm of the reduced
-        gradient, so that step is driven from Python.  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
+        gradient, so that step is driven from Python.  Tensors of the buffer that no group holds are frozen: the map then has segments
+        of their own for them and the dictionary carries "frozen", one flag per segment (mb_*_set_update_frozen) -- the step leaves
+        their parameters, moments and shadow alone and skips the launches that only they need.  None otherwise (loose tensors with gradients, a partly covered buffer, more groups or
         segments than the engine takes, fused_zero_grad off, data parallel -- whose step keeps its Python-driven exchange for classed
         optimizers, allow_dp or not): the caller then runs step() as usual.  Used by the whole-step graph (mb_bert_train_step), which
         applies the update itself."""
@@ -400,8 +437,11 @@ class AdamW(torch.optim.Optimizer):
         if planned is None:
             return None
         boundaries, classes, groups, no_decay, _ = planned
+        frozen = self._class_frozen.get(id(core))
         gs = [self.param_groups[g] for g in groups]
         marks = {} if no_decay is None else {"no_decay": list(no_decay)}
+        if frozen is not None:
+            marks["frozen"] = list(frozen)
         return dict(m=core._adam_m, v=core._adam_v, grad_scale=float(self.grad_scale), map=(boundaries, classes),
                     max_grad_norm=self._clip_value(), **marks,
                     classes=dict(lr=[float(g["lr"]) for g in gs], beta1=[float(g["betas"][0]) for g in gs],

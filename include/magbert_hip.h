@@ -318,6 +318,21 @@ int mb_bert_graph_stats(const mb_bert_engine* e, size_t* captures, size_t* launc
  *   New values never re-capture a graph: they reach the device with the step prologue, as the two groups' scalars do.
  * update_stats: the last enqueued update -- elements updated by riders inside the backward launches, elements updated by the sweep at the
  *   end of the step, and the number of segments of the map it ran under (0: the two parameter groups).  Any pointer may be NULL.
+ *   With frozen segments, ridden + swept + frozen_elems (freeze_stats) = the update range.
+ * set_update_frozen (after set_update_map, which clears every mark): frozen[s] != 0 marks segment s as one no parameter group holds
+ *   (n_segments bytes, host memory, copied; the segment still names a class, which is not looked at).  MB_ERR_MODE without a map,
+ *   MB_ERR_ARG for a wrong count.  A single-call step never changes the parameters, the bf16 shadow or the moments of such a segment, and
+ *   leaves its range of the gradient buffer zero after every step that ends with the optimizer.  It also leaves out the launches whose
+ *   whole output is frozen: the grouped weight-gradient launch (or, MB_GROUP_WGRAD=0, the four launches) of a layer whose GEMM weights
+ *   are all frozen, the scatter into a frozen word table, and the embedding backward when word, position, token-type and LayerNorm
+ *   tensors are all frozen.  The input-gradient chain always runs to the bottom (MAG is trainable), and a frozen tensor that a fused
+ *   kernel produces next to trainable ones -- a bias, one of a layer's four weights -- is still computed, then cleared by a clear-only
+ *   piece of the step's one sweep.  With clipping on, the norm is that of the trainable segments.  The marks are part of the map's
+ *   identity: a changed mark re-captures.  When marks are installed or changed the engine clears the frozen ranges of the gradient buffer
+ *   once, in front of the next single-call step, and distrusts the word-row stamps.  mb_bert_forward / _backward, the stage-driven calls
+ *   and mb_bert_backward_outputs ignore the marks and compute every gradient.
+ * freeze_stats: the last enqueued single-call step -- elements in frozen segments, weight-gradient launches (layers) left out, 1 when the
+ *   embedding backward (MAG-XLNet: the word scatter) was left out.  All zero without marks.  Any pointer may be NULL.
  * While a map is set mb_bert_train_step_dp returns MB_ERR_MODE. */
 #define MB_UPDATE_CLASSES_MAX 32
 #define MB_UPDATE_SEGMENTS_MAX 128
@@ -326,6 +341,8 @@ int mb_bert_set_update_decay(mb_bert_engine* e, int n_segments, const uint8_t* n
 int mb_bert_set_update_values(mb_bert_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                               const float* weight_decay, const int* correct_bias);
 int mb_bert_update_stats(const mb_bert_engine* e, size_t* ridden, size_t* swept, int* segments);
+int mb_bert_set_update_frozen(mb_bert_engine* e, int n_segments, const uint8_t* frozen);
+int mb_bert_freeze_stats(const mb_bert_engine* e, size_t* frozen_elems, int* wgrad_launches_skipped, int* embed_skipped);
 
 /* Gradient-norm clipping inside mb_bert_train_step.  set_grad_clip: max_norm > 0 turns it on for every later step that ends with the
  * optimizer (m, v given); max_norm <= 0 or non-finite turns it off, the default.  Sticky, like set_update_values.  Such a step updates
@@ -514,6 +531,9 @@ int mb_xlnet_set_update_decay(mb_xlnet_engine* e, int n_segments, const uint8_t*
 int mb_xlnet_set_update_values(mb_xlnet_engine* e, int n_classes, const float* lr, const float* beta1, const float* beta2, const float* eps,
                                const float* weight_decay, const int* correct_bias);
 int mb_xlnet_update_stats(const mb_xlnet_engine* e, size_t* ridden, size_t* swept, int* segments);
+/* frozen segments: as mb_bert_set_update_frozen / _freeze_stats above; a frozen layer is one whose seven GEMM weights are all frozen */
+int mb_xlnet_set_update_frozen(mb_xlnet_engine* e, int n_segments, const uint8_t* frozen);
+int mb_xlnet_freeze_stats(const mb_xlnet_engine* e, size_t* frozen_elems, int* wgrad_launches_skipped, int* embed_skipped);
 /* gradient-norm clipping inside mb_xlnet_train_step: as mb_bert_set_grad_clip / _grad_clip_stats above; the norm covers
  * [0, mb_xlnet_trainable_count) */
 int mb_xlnet_set_grad_clip(mb_xlnet_engine* e, float max_norm);

@@ -18,6 +18,9 @@
 //            class per depth with no-decay marks on the undecayed segments otherwise (mb_*_set_update_decay) -- the same update
 //   --max_grad_norm X (--graph 1|2, no --dp; 0 = off): gradient-norm clipping inside the step (mb_*_set_grad_clip); the norm and coefficient
 //            of the last update are printed
+//   --freeze_layers N, --freeze_emb 0|1 (--graph 1|2, no --dp): the lowest N layers / the embedding tables are in no update class
+//            (mb_*_set_update_frozen): no weight-gradient launch for those layers, no embedding backward; composes with --layer_decay and
+//            --max_grad_norm.  Without --layer_decay the rest is the two parameter groups as a two-class map.  Prints mb_*_freeze_stats.
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
 // Prints one line per run: ms/step (HIP events around the K timed steps), host enqueue ms/step, samples/s, final loss.
@@ -46,6 +49,7 @@ int main(int argc, char** argv) {
     int steps = 30, warmup = 5, B = 48, L = 50, V = 47, A = 74, layers = 12, graph = 0, h2d = 0, nbatch = 4, dtype = MB_DT_BF16;
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
     double layer_decay = 1.0, head_lr_mult = 1.0, max_grad_norm = 0.0;
+    int freeze_layers = 0, freeze_emb = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -58,9 +62,10 @@ int main(int argc, char** argv) {
         else if (k == "--model") xl = strcmp(v, "xlnet") == 0;       // MAG-XLNet (BASELINE.json configs[3]): the single-call step only (--graph 1|2)
         else if (k == "--layer_decay") layer_decay = atof(v); else if (k == "--head_lr_mult") head_lr_mult = atof(v);
         else if (k == "--max_grad_norm") max_grad_norm = atof(v);
+        else if (k == "--freeze_layers") freeze_layers = atoi(v); else if (k == "--freeze_emb") freeze_emb = atoi(v);
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -153,15 +158,17 @@ int main(int argc, char** argv) {
     const float lr = 1e-5f, b1 = 0.9f, b2 = 0.999f, eps = 1e-6f, wd = 0.01f;
     int t_opt = 0;
     const bool classed = layer_decay != 1.0 || head_lr_mult != 1.0;
+    const bool freezing = freeze_layers > 0 || freeze_emb != 0;
     int n_classes = 0, n_segments = 0;
-    if (classed) {
-        if (!graph || dp) { fprintf(stderr, "--layer_decay / --head_lr_mult: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
+    if (classed || freezing) {
+        if (!graph || dp) { fprintf(stderr, "--layer_decay / --head_lr_mult / --freeze_*: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
+        if (freeze_layers > layers) { fprintf(stderr, "--freeze_layers: at most %d\n", layers); return 1; }
         // depth 0 = embeddings (and any other encoder tensor), l + 1 = layer l, layers + 1 = MAG / pooler / heads
         // Two classes per depth (decayed / not) while they fit the table; deeper models share one class per depth and mark the
         // no-decay segments (mb_*_set_update_decay) -- the same update either way
-        const bool split = 2 * (layers + 2) <= MB_UPDATE_CLASSES_MAX;
+        const bool split = !classed || 2 * (layers + 2) <= MB_UPDATE_CLASSES_MAX;
         if (layers + 2 > MB_UPDATE_CLASSES_MAX) { fprintf(stderr, "--layer_decay / --head_lr_mult: at most %d layers\n", MB_UPDATE_CLASSES_MAX - 2); return 1; }
-        std::vector<uint8_t> marks;
+        std::vector<uint8_t> marks, frozen;
         std::vector<int> slot_of(2 * (layers + 2), -1);
         std::vector<size_t> bounds; std::vector<int> cls;
         std::vector<float> c_lr, c_b1, c_b2, c_eps, c_wd; std::vector<int> c_cb;
@@ -179,23 +186,35 @@ int main(int argc, char** argv) {
             else if (s.find("MAG.") != std::string::npos || s.find("pooler.") != std::string::npos || s.find("classifier.") != std::string::npos ||
                      s.find("sequence_summary.") != std::string::npos || s.find("logits_proj.") != std::string::npos) depth = layers + 1;
             const bool no_decay = s.find("bias") != std::string::npos || s.find("LayerNorm.weight") != std::string::npos;
-            const int key = 2 * depth + ((split && no_decay) ? 1 : 0);
+            // frozen: the lowest layers, the embedding tables (MAG-BERT: with their LayerNorm) -- in no class, a segment of their own
+            const bool fz = (depth >= 1 && depth <= freeze_layers) ||
+                            (freeze_emb && (s.find("embeddings.") != std::string::npos || s.find("word_embedding") != std::string::npos));
+            if (fz) {
+                if (cls.empty() || !frozen.back()) { bounds.push_back(off); cls.push_back(0); marks.push_back(0); frozen.push_back(1); }
+                end = (off + numel + 63) / 64 * 64;
+                continue;
+            }
+            const int key = classed ? 2 * depth + ((split && no_decay) ? 1 : 0) : (no_decay ? 1 : 0);
             if (slot_of[key] < 0) {
                 slot_of[key] = n_classes++;
                 c_lr.push_back(depth == layers + 1 ? (float)(lr * head_lr_mult) : (float)(lr * pow(layer_decay, layers + 1 - depth)));
                 c_b1.push_back(b1); c_b2.push_back(b2); c_eps.push_back(eps); c_wd.push_back((split && no_decay) ? 0.f : wd); c_cb.push_back(1);
             }
             const uint8_t mark = (!split && no_decay) ? 1 : 0;
-            if (cls.empty() || cls.back() != slot_of[key] || marks.back() != mark) { bounds.push_back(off); cls.push_back(slot_of[key]); marks.push_back(mark); }
+            if (cls.empty() || frozen.back() || cls.back() != slot_of[key] || marks.back() != mark) {
+                bounds.push_back(off); cls.push_back(slot_of[key]); marks.push_back(mark); frozen.push_back(0);
+            }
             end = (off + numel + 63) / 64 * 64;
         }
         bounds.push_back(end);
         n_segments = (int)cls.size();
         if (xl) { MCK(mb_xlnet_set_update_map(ex, n_classes, n_segments, bounds.data(), cls.data()));
                   if (!split) MCK(mb_xlnet_set_update_decay(ex, n_segments, marks.data()));
+                  if (freezing) MCK(mb_xlnet_set_update_frozen(ex, n_segments, frozen.data()));
                   MCK(mb_xlnet_set_update_values(ex, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
         else { MCK(mb_bert_set_update_map(e, n_classes, n_segments, bounds.data(), cls.data()));
                if (!split) MCK(mb_bert_set_update_decay(e, n_segments, marks.data()));
+               if (freezing) MCK(mb_bert_set_update_frozen(e, n_segments, frozen.data()));
                MCK(mb_bert_set_update_values(e, n_classes, c_lr.data(), c_b1.data(), c_b2.data(), c_eps.data(), c_wd.data(), c_cb.data())); }
     }
     if (max_grad_norm > 0.0) {
@@ -253,6 +272,12 @@ int main(int argc, char** argv) {
         if (xl) MCK(mb_xlnet_update_stats(ex, &ridden, &swept, &segs)); else MCK(mb_bert_update_stats(e, &ridden, &swept, &segs));
         printf("step_bench update: classes=%d segments=%d ridden=%zu swept=%zu (layer_decay=%g head_lr_mult=%g)\n", n_classes, segs, ridden, swept,
                layer_decay, head_lr_mult);
+        if (freezing) {
+            size_t fe = 0; int wg = 0, emb = 0;
+            if (xl) MCK(mb_xlnet_freeze_stats(ex, &fe, &wg, &emb)); else MCK(mb_bert_freeze_stats(e, &fe, &wg, &emb));
+            printf("step_bench freeze: freeze_layers=%d freeze_emb=%d frozen_elems=%zu wgrad_launches_skipped=%d embed_skipped=%d\n", freeze_layers,
+                   freeze_emb, fe, wg, emb);
+        }
         if (max_grad_norm > 0.0) {
             float norm = 0.f, coef = 0.f;
             if (xl) MCK(mb_xlnet_grad_clip_stats(ex, &norm, &coef, st)); else MCK(mb_bert_grad_clip_stats(e, &norm, &coef, st));
