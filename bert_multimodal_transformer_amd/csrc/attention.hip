@@ -22,15 +22,7 @@
 
 namespace mb {
 
-// The bias that every key of the sample carries: kMaskNeg when the sample has no real key at all (a fully padded sample), else 0.
-// The softmax does not depend on a bias common to all keys, but fp32 holds score / 8 - 10000 to 4.9e-4 only, so such a sample's
-// probabilities came out 4e-4 off the exact ones in fp32.  It is taken off the key biases before they are added; with one real key
-// it is 0 and x - 0 is x, the same bits as before.  Every wave works it out for itself (L <= 128: two mask words per lane).
-__device__ __forceinline__ float common_key_bias(const int64_t* __restrict__ mrow, int L, int lane) {
-    bool live = false;
-    for (int j = lane; j < L; j += 64) live |= mrow[j] != 0;
-    return __ballot(live) ? 0.0f : kMaskNeg;
-}
+// (the -10000 of a fully padded sample: common_key_bias, attn_common.h -- two mask words per lane at L <= 128)
 
 // =============================================================================================== forward
 template <class T, int LP, int NW>

@@ -52,8 +52,10 @@ struct TileStage {
     }
 };
 
-__device__ __forceinline__ float key_bias(const int64_t* __restrict__ mrow, int j, int L) {
-    return j < L ? (1.0f - (float)mrow[j]) * kMaskNeg : kPadNeg;
+// shift: common_key_bias of the sample (attn_common.h): kMaskNeg when it has no real key at all, else 0 (x - 0 is x: the same bits).
+// All four sweeps that form scores take it off, so the m the forward stores is the m the backward recomputes against.
+__device__ __forceinline__ float key_bias(const int64_t* __restrict__ mrow, int j, int L, float shift) {
+    return j < L ? (1.0f - (float)mrow[j]) * kMaskNeg - shift : kPadNeg;
 }
 
 // this lane's MFMA fragment of row `row` of a token-major head (frag_nat's layout, straight from global memory; rows >= L are zero)
@@ -117,13 +119,14 @@ __global__ void MB_TILED_BOUNDS(T, true) attn_tiled_fwd_kernel(const T* __restri
     const int i = (blockIdx.x % nqb) * 64 + wave * 16 + (lane & 15);      // this lane's query row
     const int nkt = (L + 63) / 64;
 
+    const float shift = common_key_bias(mrow, L, lane);      // (before the fragments are loaded: a scalar from here on)
     TileStage<T, 2> st;
     float mb = 0.f;
     auto issue = [&](int t) {
         const T* const src[2] = {base + (size_t)t * 64 * ld + H, base + (size_t)t * 64 * ld + 2 * H};
         const size_t lds[2] = {ld, ld};
         st.issue(src, lds, L - t * 64);
-        if (threadIdx.x < 64) mb = key_bias(mrow, t * 64 + threadIdx.x, L);
+        if (threadIdx.x < 64) mb = key_bias(mrow, t * 64 + threadIdx.x, L, shift);
     };
     auto commit = [&](int slot) {
         char* const img[2] = {smem[slot], smem[slot] + IMG};
@@ -243,13 +246,14 @@ __global__ void MB_TILED_BOUNDS(T, false) attn_tiled_dq_kernel(const T* __restri
     const int i = (blockIdx.x % nqb) * 64 + wave * 16 + (lane & 15);
     const int nkt = (L + 63) / 64;
 
+    const float shift = common_key_bias(mrow, L, lane);      // (before the fragments are loaded: a scalar from here on)
     TileStage<T, 2> st;
     float mb = 0.f;
     auto issue = [&](int t) {
         const T* const src[2] = {base + (size_t)t * 64 * ld + H, base + (size_t)t * 64 * ld + 2 * H};
         const size_t lds[2] = {ld, ld};
         st.issue(src, lds, L - t * 64);
-        if (threadIdx.x < 64) mb = key_bias(mrow, t * 64 + threadIdx.x, L);
+        if (threadIdx.x < 64) mb = key_bias(mrow, t * 64 + threadIdx.x, L, shift);
     };
     auto commit = [&](int slot) {
         char* const img[2] = {smem[slot], smem[slot] + IMG};
@@ -380,7 +384,7 @@ __global__ void MB_TILED_BOUNDS(T, false) attn_tiled_dkdv_kernel(const T* __rest
         kf[sl] = frag_row<T>(base + H, ld, j, L, sl, lane);
         vf[sl] = frag_row<T>(base + 2 * H, ld, j, L, sl, lane);
     }
-    const float mbj = key_bias(mask + (size_t)b * L, j, L);
+    const float mbj = key_bias(mask + (size_t)b * L, j, L, common_key_bias(mask + (size_t)b * L, L, lane));
     commit(0);
     __syncthreads();
 

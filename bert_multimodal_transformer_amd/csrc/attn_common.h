@@ -167,5 +167,15 @@ constexpr float kMaskNeg = -10000.0f;     // transformers 3.0.2 get_extended_att
 // pad with -inf instead (xlnet_attention.hip kXlPad, xlnet_attention_tiled.hip)
 constexpr float kPadNeg = -1.0e30f;
 
+// The bias that every key of the sample carries: kMaskNeg when the sample has no real key at all (a fully padded sample), else 0.
+// The softmax does not depend on a bias common to all keys, but fp32 holds score / 8 - 10000 to 4.9e-4 only, so such a sample's
+// probabilities came out 4e-4 off the exact ones in fp32.  It is taken off the key biases before they are added; with one real key
+// it is 0 and x - 0 is x, the same bits as before.  Every wave works it out for itself (L <= 512: up to eight mask words per lane);
+// wave-uniform, so every kernel of a forward / backward pair shifts by the same amount and the saved row maxima stay consistent.
+__device__ __forceinline__ float common_key_bias(const int64_t* __restrict__ mrow, int L, int lane) {
+    bool live = false;
+    for (int j = lane; j < L; j += 64) live |= mrow[j] != 0;
+    return __ballot(live) ? 0.0f : kMaskNeg;
+}
 
 }  // namespace mb

@@ -24,7 +24,8 @@
 //       bwd_kv  (key blocks)     : dk = G^T (q + r_w_bias), dv = Pd^T dO over the query tiles, both operands read k-major
 //       bwd_pos (position blocks): dkr[p] = sum_i G[i, p - L + i] (q_i + r_r_bias): 64 rows of dkr, sweeping the query tiles that hold
 //                                  a piece of the block's shifted diagonal band
-// Row statistics: two fp32 planes of B*nh*L rows -- m | 1/l.  The backward's D_i = dvec_i . vec_i needs the forward's vec.
+// Row statistics: two fp32 planes of B*nh*L rows -- m | 1/l.  The backward's D_i = dvec_i . vec_i needs the forward's vec in fp32; in
+// bf16, where vec is rounded, bwd_q forms D_i = sum_j Pd_ij (dvec V^T)_ij in a sweep of its own instead.
 // Dropout masks: counter hash (common.h), index ((b*nh + h)*L + i)*L + j over the true L, as in xlnet_attention.hip.
 #include "attn_common.h"
 
@@ -406,11 +407,13 @@ __global__ void MB_XLT_BOUNDS xl_tiled_bwd_q_kernel(const T* __restrict__ qkv, c
     for (int sl = 0; sl < X::DSL; ++sl) {
         qf[sl] = xfrag_row<T>(base, ld, i, L, sl, lane);
         of[sl] = xfrag_row<T>(dvec + (size_t)b * L * H + h * 64, H, i, L, sl, lane);
-        const F cf = xfrag_row<T>(vec + (size_t)b * L * H + h * 64, H, i, L, sl, lane);
+        if constexpr (sizeof(T) == 4) {
+            const F cf = xfrag_row<T>(vec + (size_t)b * L * H + h * 64, H, i, L, sl, lane);
 #pragma unroll
-        for (int e = 0; e < C::EPV; ++e) dpart += (float)of[sl][e] * (float)cf[e];
+            for (int e = 0; e < C::EPV; ++e) dpart += (float)of[sl][e] * (float)cf[e];
+        }
     }
-    const float D = quad_sum(dpart);                  // D_i = dvec_i . vec_i (vec carries dropout and head_scale)
+    float D = quad_sum(dpart);                        // fp32: D_i = dvec_i . vec_i (vec carries dropout and head_scale); bf16: below
     float mi = 0.f, invi = 0.f;
     if (i < L) { mi = stats[(size_t)bh * L + i]; invi = stats[plane + (size_t)bh * L + i]; }
     sm.commit_kv(0); sm.commit_kr(0);
@@ -429,6 +432,40 @@ __global__ void MB_XLT_BOUNDS xl_tiled_bwd_q_kernel(const T* __restrict__ qkv, c
     const uint32_t rowidx = ((uint32_t)bh * L + (uint32_t)i) * L;
     const uint8_t* prow = (xp.perm != nullptr && i < L) ? xp.perm + ((size_t)b * L + i) * L : nullptr;
     const size_t srow = ((size_t)bh * LP + (i < LP ? i : 0)) * LP;      // scratch row of this lane
+    if constexpr (sizeof(T) == 2) {
+        // bf16: D_i = sum_j Pd_ij (dvec V^T)_ij from a sweep of its own, in fp32 and with the very products the main sweep forms.  The
+        // forward's vec is rounded to bf16, and dvec_i . vec_i carries that rounding (2^-9 of |vec|, 64 terms) into every G_ij = P_ij
+        // (.. - D_i): where a row's probability sits on ONE key G is exactly zero, and what came out instead was 4e-3 per row --
+        // summed over the rows of a fully padded sample into dkr[L] (their diagonals all map there): 7.3e-2 at L = 200, 1.5e-1 at
+        // L = 449 against max|dkr| 1.0, and 7.8e-3 at L = 1 where dkr is zero.  Costs the forward's products once more.
+        float dacc = 0.f;
+#pragma unroll 1
+        for (int t = 0; t < nkt; ++t) {
+            int lane = threadIdx.x & 63;          // opaque per tile: see the main sweep
+            asm volatile("" : "+v"(lane));
+            const int g = lane >> 4, ii = lane & 15;
+            sm.ahead(t, nkt);
+            const char* Vi = smem + (t & 1) * 2 * X::IMG + X::IMG;
+            f32x4 s[4];
+            xl_tile_scores<T, 6>(smem, t, qf, Ss, wstart, coff, i, si, e0, e1, prow, 0, lane, s);
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                f32x4 dpj = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int sl = 0; sl < X::DSL; ++sl) mma16(dpj, frag_nat<T>(Vi, X::PIT, jt * 16 + ii, sl, lane), of[sl]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = i < L ? __expf(s[jt][r] - mi) * invi : 0.f;
+                    const float dm = drop_mult(drop, rowidx + t * 64 + jt * 16 + g * 4 + r) * hs;
+                    dacc += (p * dm) * dpj[r];
+                }
+            }
+            sm.behind(t, nkt);
+            __syncthreads();
+        }
+        D = quad_sum(dacc);
+        if (nkt > 1) sm.prime();              // (one tile: the rings still hold tile 0 and chunks 0, 1)
+    }
     float g0 = 0.f, g1 = 0.f;
     f32x4 oa[4], ob[4];                // dq pieces: G.K and Gshift.KR
 #pragma unroll

@@ -6,16 +6,14 @@ NaN in everything the kernels own, and the query stream's fully masked rows.
 
 Bounds: test_ops_gpu.close() times 2 for forward quantities and times 3 for backward ones, the factors of the tiled tests
 (test_long_seq_gpu.py, test_xlnet_long_gpu.py).  B = 2 throughout; the fp64 references at L <= 128 take milliseconds."""
-import ctypes as C
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from bert_multimodal_transformer_amd import _lib, rng
-from attn_op_helpers import NAMES, _XlOp, _errors, xl_lp
-from test_ops_gpu import DEV, DTS, _attn_ref, close, rnd, stream
+from bert_multimodal_transformer_amd import _lib
+from attn_op_helpers import NAMES, _BertOp, _XlOp, _errors, xl_lp
+from test_ops_gpu import DEV, DTS, close, stream
 
 
 # ------------------------------------------------------------------------------------------------------------ MAG-XLNet
@@ -121,40 +119,6 @@ def test_resident_query_stream_fully_masked_row(dt, tdt, L):
 
 
 # ------------------------------------------------------------------------------------------------------------ MAG-BERT
-class _BertOp(object):
-    """one op-level case of the BERT attention core: inputs, the fp64 reference (ctx, dqkv, the probabilities after dropout and head
-    mask) and the device tensors"""
-
-    def __init__(self, dt, tdt, S, nh, p, mask, hs=None):
-        B = 2
-        self.dt, self.tdt, self.B, self.S, self.nh = dt, tdt, B, S, nh
-        H = nh * 64
-        self.qkv = rnd((B * S, 3 * H), 1, tdt, 2.0).requires_grad_(True)
-        self.dctx = rnd((B * S, H), 2, tdt)
-        self.key, pm = None, torch.ones(B, nh, S, S, dtype=torch.float64)
-        if p > 0:
-            self.key = _lib.make_dropkey(7, 5, 16, p)
-            pm = torch.from_numpy(rng.keep_mult(B * nh * S * S, rng.make_key(7, 5, 16, p))).view(B, nh, S, S).double()
-        if hs is not None:
-            pm = pm * hs.double()[None, :, None, None]
-        self.ctx = _attn_ref(self.qkv.double(), mask, B, S, nh, pm)
-        self.ctx.backward(self.dctx.double())
-        q, k, _ = self.qkv.detach().double().view(B, S, 3, nh, 64).permute(2, 0, 3, 1, 4)
-        self.soft = torch.softmax(q @ k.transpose(-1, -2) / 8.0 + (1.0 - mask[:, None, None, :].double()) * -10000.0, -1)
-        self.probs = self.soft * pm
-        self.qd, self.md, self.dcd = self.qkv.detach().to(DEV, tdt), mask.to(DEV), self.dctx.to(DEV, tdt)
-        self.hsd = hs.to(DEV) if hs is not None else None
-        self.kp = C.byref(self.key) if self.key is not None else None
-
-    def errors(self, what, **got):
-        ref = dict(ctx=self.ctx.detach(), dqkv=self.qkv.grad, probs=self.probs, dbias=self.qkv.grad.double().sum(0))
-        for k, g in got.items():
-            print("resident bert attention %s %s S=%d nh=%d %s: max|err| %.3e (max|ref| %.3e)"
-                  % (what, self.tdt, self.S, self.nh, k, float((g.float().cpu().double() - ref[k].double()).abs().max()), float(ref[k].abs().max())))
-        for k, g in got.items():
-            close(g.float(), ref[k].float(), self.dt, what + " " + k, 2.0 if k in ("ctx", "probs") else 3.0)
-
-
 def _bert_plain(dt, tdt, S, nh, p, mask, what):
     """mb_attention_forward / _backward (NaN in both outputs before the calls): ctx and dqkv against fp64"""
     c = _BertOp(dt, tdt, S, nh, p, mask)

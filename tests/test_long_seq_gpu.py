@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 from bert_multimodal_transformer_amd import AdamW, BertConfig, MAG_BertForSequenceClassification, MultimodalConfig, _lib, rng
 from bert_multimodal_transformer_amd import get_linear_schedule_with_warmup
 from oracle import mag_bert_ref as R, weights
+from attn_op_helpers import _tiled
 from test_model_gpu import DEV, LOOSE_BF16, _grad_report, _Replay, build, oracle, tb
 from test_ops_gpu import _attn_ref, close, rnd, stream
 
@@ -60,23 +61,6 @@ def oracle_logits(o, b):
 
 
 # ------------------------------------------------------------------------------------------------------------ op level
-def _tiled(dt, tdt, qd, md, dctx_d, B, S, nh, key, hs=None, probs=False, dbias=False):
-    L = _lib.lib()
-    H = nh * 64
-    stats = torch.zeros(L.mb_attention_tiled_stats_bytes(B, S, nh) // 4, dtype=torch.float32, device=DEV)
-    out = torch.zeros(B * S, H, dtype=tdt, device=DEV)
-    pr = torch.zeros(B, nh, S, S, dtype=torch.float32, device=DEV) if probs else None
-    kp = C.byref(key) if key is not None else None
-    _lib.check(L.mb_attention_tiled_forward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(out), _lib.ptr(stats), B, S, nh, kp,
-                                            _lib.ptr(hs), _lib.ptr(pr), stream()))
-    dq = torch.zeros(B * S, 3 * H, dtype=tdt, device=DEV)
-    db = torch.zeros(3 * H, dtype=torch.float32, device=DEV) if dbias else None
-    _lib.check(L.mb_attention_tiled_backward(dt, _lib.ptr(qd), _lib.ptr(md), _lib.ptr(out), _lib.ptr(dctx_d), _lib.ptr(stats),
-                                             _lib.ptr(dq), _lib.ptr(db), B, S, nh, kp, _lib.ptr(hs), stream()))
-    torch.cuda.synchronize()
-    return out, dq, pr, db
-
-
 @pytest.mark.parametrize("dt,tdt", DTS)
 @pytest.mark.parametrize("S", [64, 128, 129, 200, 256, 384, 512])
 @pytest.mark.parametrize("p", [0.0, 0.1])
