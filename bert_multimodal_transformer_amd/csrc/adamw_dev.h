@@ -61,11 +61,43 @@ template <bool NT> __device__ __forceinline__ void adam_update_store(AdamQuad q,
     if (shadow && i >= sh_begin && i < sh_end) store4(shadow + i, q.p);
 }
 
+// The update loop of adamw.hip's kernels: a 256-thread block walks quads [begin, end) of the buffers (`begin` is this thread's first
+// quad) with two quads of every stream in flight.  skip_on (kernels.h WordSkip): a quad of [ws.begin, ws.end) whose row carries no
+// stamp `stamp_no` gets g = +0.0f without the load and keeps the zero it has without the store; a wave may straddle two rows (768
+// floats = three waves of quads), which costs a divergent load.  A literal `false` folds all of that away.
+// (The element index is formed inside the bounds check: hoisted above it, the single-range kernel takes 68 VGPRs instead of 62 and
+//  loses its eighth wave per SIMD -- tests/test_host_cpu.py::test_adamw_kernels_keep_their_residency.)
+template <bool NT>
+__device__ __forceinline__ void adam_span(float* p, float* g, float* m, float* v, bf16* shadow, size_t begin, size_t end, const AdamArgs& a,
+                                          size_t n_decay, size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, int zero_grad,
+                                          bool skip_on, const WordSkip& ws, uint32_t stamp_no) {
+    constexpr int UNR = 2; const size_t stride = 256;
+    const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+    const float decay = a.lr * a.weight_decay;
+    for (size_t i4 = begin; i4 < end; i4 += stride * UNR) {
+        AdamQuad q[UNR];
+        bool live[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            live[u] = true;
+            if (i4 + u * stride < end) {
+                const size_t i = (i4 + u * stride) * 4;
+                if (skip_on && i >= ws.begin && i < ws.end) live[u] = ws.stamp[(uint32_t)(i - ws.begin) / ws.row_len] == stamp_no;
+                q[u] = adam_load<NT>(p, g, m, v, i, live[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u)
+            if (i4 + u * stride < end)
+                adam_update_store<NT>(q[u], p, g, m, v, shadow, (i4 + u * stride) * 4, a, omb1, omb2, decay, n_decay, sh_begin, sh_end, keep_begin,
+                                      keep_end, live[u] ? zero_grad : 0);
+    }
+}
 
 // One rider workgroup (kernels.h AdamRide): workgroup `rb` of `r.blocks` owns one contiguous range of every stream.  A rider has a
 // CU's memory pipeline to itself but only its own 4-8 waves to cover the HBM latency with, so the loop is a two-stage software
 // pipeline: the loads of one half-iteration (UNR quads per stream and thread) are in flight while the other half is updated and
-// stored.  Same arithmetic, same order as adamw_var_kernel (adam_update_store, contraction off): the same bits.
+// stored.  Same arithmetic, same order as adam_span (adam_update_store, contraction off): the same bits.
 template <int NTHREADS, int UNR>
 __device__ __forceinline__ void adam_ride_block(const AdamRide& r, int rb) {
     if (r.n4 == 0) return;

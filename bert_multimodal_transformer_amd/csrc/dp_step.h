@@ -8,6 +8,7 @@
 // An engine E gives the templates what differs by name through four accessors next to n_update_end() -- n_layers(), layer_begin(l) (flat
 // offset of layer l's first GEMM weight), layers_end() (end of the layers' GEMM weights) and width() -- and its prepare-pass,
 // forward-range and backward functions as callables (they are file-static in each engine's translation unit).
+// The optimizer end of the single-process step (enqueue_update) lives here too: it reads the engines through the same accessors.
 #pragma once
 #include "engine_common.h"
 #include "comm.h"
@@ -25,6 +26,49 @@ int adamw_decay_range(E* e, float* m, float* v, size_t b, size_t en, hipStream_t
     const size_t kb = keep ? clampr(e->stale_begin) : 0, ke = keep ? clampr(e->stale_end) : 0;
     void* sh = e->c.dtype == DT_BF16 ? (void*)(e->SH + b * 2) : nullptr;
     return adamw_step(e->P + b, e->G + b, m + b, v + b, sh, en - b, en - b, shb, she, none, 1, st, e->adam_state(e->ws), kb, ke);
+}
+
+// The optimizer end of a single-process single-call step, behind the engine's backward: the clip (StepMixin::clip_step: the whole
+// gradient is final, its norm and the coefficient go into the scalars the sweep reads), the update statistics and the sweep of what
+// the riders (MB_ADAMW_RIDE) left -- they took [ride_cursor, layers_end()) of the decay slab when `ride`.  On top of dp_step's
+// accessors an engine gives word_skip(ws): the WordSkip of its word table when it can vouch for untouched rows, {} otherwise.
+//   classed step (kernels.h AdamPieces): the ranges cut at the segment boundaries, every piece with its class's slot, ONE launch;
+//   unclassed: what the riders left of the layers, the rest of the decay slab, the no-decay slab -- ONE launch over that table
+//   (one_sweep; MB_ADAMW_ONE_SWEEP=0 with a word skip: one launch per range, each a one-piece table), which leaves the gradients of
+//   the word rows this update's batches did not touch alone (WordSkip, StepMixin::stamp_live: the prologue put the verdict of THIS step
+//   into device memory, so the captured launch is the same either way);
+//   neither: adamw_step per range.
+template <class E>
+int enqueue_update(E* e, float* m, float* v, bool ride, bool clip, hipStream_t st) {
+    char* ws = e->ws;
+    const int NL = e->n_layers();
+    const size_t nd = e->n_decay, n = e->n_update_end(), wend = e->layers_end();
+    if (clip) CK(e->enqueue_clip(e->G, n, ws, st));
+    CK(e->prof_mark(2 * NL, st));
+    e->upd_ridden = ride ? wend - e->ride_cursor - e->ride_hopped : 0; e->upd_swept = n - e->upd_ridden - e->frz_elems;
+    e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
+    const bool classed = e->n_classes > 0;
+    const WordSkip skip = e->word_skip(ws);
+    if (classed || e->one_sweep || skip.stamp) {
+        const bool keep = e->keep_in_step(), one = classed || e->one_sweep;
+        const size_t kb = keep ? e->stale_begin : 0, ke = keep ? e->stale_end : 0;
+        const int slots[2] = {0, 1};
+        AdamPieces all;
+        if (classed) CK(e->sweep_pieces(all, 0, ride ? e->ride_cursor : wend, wend, n, true, kb, ke));
+        else CK(e->cut_pieces(all, {0, nd, n}, slots, nullptr, 0, ride ? e->ride_cursor : 0, ride ? wend : 0, n));
+        for (int k = 0; k < (one ? 1 : all.count); ++k) {
+            AdamPieces p = all;
+            if (!one) { p = AdamPieces{}; p.begin4[0] = all.begin4[k]; p.start4[1] = all.start4[k + 1] - all.start4[k]; p.slot[0] = all.slot[k]; p.count = p.clear_first = 1; }
+            CK(adamw_sweep(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, p, e->sh_begin, e->sh_end, kb, ke,
+                           classed ? e->class_state(ws) : e->adam_state(ws), skip, st));
+        }
+        return e->prof_mark(2 * NL + 1, st);
+    }
+    const AdamArgs none = {};
+    if (ride) CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));       // what no launch carried (layer 0 always)
+    CK(adamw_decay_range(e, m, v, ride ? wend : 0, nd, st));
+    CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
+    return e->prof_mark(2 * NL + 1, st);
 }
 
 // AdamW over [b, en) of the decay slab inside a data-parallel step.  Sharded update (comm->shard): of every chunk of layer GEMM weights

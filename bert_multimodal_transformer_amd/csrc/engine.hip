@@ -35,6 +35,11 @@ struct mb_bert_engine : StepMixin {
     size_t layer_end(int l) const { return l + 1 < c.num_layers ? lo[l + 1].wqkv : wp; }
     // frozen marks (StepMixin::seg_frozen): the five embedding tensors are all frozen -- a single-call step runs no embedding backward
     bool embed_all_frozen() const { return range_frozen(word, mag_whv) && range_frozen(emb_lnw, bp); }
+    // (dp_step.h enqueue_update: the sweep may leave the word rows no batch of this update touched alone -- StepMixin::stamp_live)
+    WordSkip word_skip(char* w) const {
+        if (!(stamp_off != 0 && stamp_enable && idcnt_enable)) return {};
+        return WordSkip{stamp_table(w), stamp_state(w), word, word + (size_t)c.vocab_size * c.hidden_size, (uint32_t)c.hidden_size};
+    }
     // workspace
     MagWs mw;
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
@@ -64,7 +69,6 @@ struct mb_bert_engine : StepMixin {
     int ride_blocks = 0;           // MB_ADAMW_RIDE_BLOCKS: rider workgroups per weight-gradient launch (0 = every free slot)
     float* ride_m = nullptr; float* ride_v = nullptr;       // Adam moments of the step being enqueued, when riders apply to it
     size_t ride_cursor = 0;                                 // the riders of the step being enqueued have taken [ride_cursor, wp) of the decay slab
-    bool one_sweep = true;                                  // MB_ADAMW_ONE_SWEEP=0: the end-of-step sweep as three launches (kernels.h AdamRanges)
     long ride_params = 0;                                   // MB_ADAMW_RIDE_PARAMS: parameters per launch (0 = by the token count)
     // (ride_opts.dgrad: riders also in the two narrow dgrad launches of a layer -- ffn1, qkv: 456 64 x 64 tiles in 768 block slots at T = 2400;
     //  kernels.h gemm_nn_ride_launch -- and, at 2, in the 128 x 128 ffn2 dgrad: 456 tiles in 512 slots, 56 CUs hold one tile.
@@ -813,7 +817,7 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
 // reference for the graph; also what runs while profiling events are on).  The prologue also converts the modality tensors into
 // MAG's packed GEMM operands, counts the occurrences of every token id and clears the loss accumulator (rowops.hip).
 
-// The kernels of the step: forward, backward, optimizer (adamw_decay_range: dp_step.h)
+// The kernels of the step: forward, backward, optimizer (enqueue_update: dp_step.h)
 static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* loss, float* loss_run, float* m, float* v,
                         float loss_scale, hipStream_t st) {
     char* ws = e->ws;
@@ -836,8 +840,7 @@ static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* l
     e->ride_cursor = e->wp;
     // frozen marks: what this step's backward will not write (StepMixin::frz_unwritten) -- the GEMM weights of fully frozen layers, a
     // frozen word table, every embedding tensor when all five are frozen.  The riders and the sweep are cut around them.
-    e->frz_unwritten.clear(); e->ride_hopped = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
-    e->frz_elems = e->any_frozen ? e->frozen_total() : 0;
+    e->begin_step_marks();
     if (e->skipping()) {
         for (int l = 0; l < NL; ++l) if (e->range_frozen(e->lo[l].wqkv, e->layer_end(l))) e->note_unwritten(e->lo[l].wqkv, e->layer_end(l));
         if (e->embed_all_frozen()) { e->note_unwritten(e->word, e->mag_whv); e->note_unwritten(e->emb_lnw, e->bp); }
@@ -847,60 +850,7 @@ static int enqueue_step(mb_bert_engine* e, int B, int L, float* logits, float* l
     const int rb = mb_bert_backward(e, nullptr, lab, loss_scale, 0, NL + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
-    if (m && v) {
-        const AdamArgs none = {};
-        const size_t nd = e->n_decay, n = e->n_params;
-        if (clip) CK(e->enqueue_clip(e->G, n, ws, st));      // the whole gradient is final: its norm, and the coefficient into the scalars the sweep below reads
-        CK(e->prof_mark(2 * NL, st));
-        e->upd_ridden = ride ? e->wp - e->ride_cursor - e->ride_hopped : 0; e->upd_swept = n - e->upd_ridden - e->frz_elems;
-        e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
-        if (e->n_classes > 0) {
-            // Classed step (kernels.h AdamPieces): the same ranges cut at the segment boundaries, every piece with its class's slot, ONE
-            // launch; the word rows and the keep range as below
-            AdamPieces pieces;
-            const bool keep = e->keep_in_step();
-            CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wp, e->wp, n, true, keep ? e->stale_begin : 0, keep ? e->stale_end : 0));
-            const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
-            WordSkip ws_ = {};
-            if (skip) ws_ = WordSkip{e->stamp_table(ws), e->stamp_state(ws), e->word, e->word + (size_t)e->c.vocab_size * e->c.hidden_size,
-                                      (uint32_t)e->c.hidden_size};
-            CK(adamw_sweep_classed(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, pieces, e->sh_begin, e->sh_end,
-                                   keep ? e->stale_begin : 0, keep ? e->stale_end : 0, e->class_state(ws), ws_, st));
-            CK(e->prof_mark(2 * NL + 1, st));
-            return MB_OK;
-        }
-        // The sweep proper: what the riders left of the layers, the rest of the decay slab, the no-decay slab.  ONE launch over that list
-        // (kernels.h AdamRanges; MB_ADAMW_ONE_SWEEP=0: one launch per range), which leaves the gradients of the word rows this update's
-        // batches did not touch alone when the engine can vouch for their zeros (WordSkip, StepMixin::stamp_live: the prologue put the
-        // verdict of THIS step into device memory, so the captured launch is the same either way).  Both off: the three launches below.
-        const bool skip = e->stamp_off != 0 && e->stamp_enable && e->idcnt_enable;
-        if (e->one_sweep || skip) {
-            AdamRanges all = {};
-            auto add = [&](size_t b, size_t en, int slot) {
-                if (en > b) { all.begin[all.count] = b; all.n[all.count] = en - b; all.slot[all.count] = slot; ++all.count; }
-            };
-            if (ride) add(0, e->ride_cursor, 0);
-            add(ride ? e->wp : 0, nd, 0);
-            add(nd, n, 1);
-            const bool keep = e->keep_in_step();
-            WordSkip ws_ = {};
-            if (skip) ws_ = WordSkip{e->stamp_table(ws), e->stamp_state(ws), e->word, e->word + (size_t)e->c.vocab_size * e->c.hidden_size,
-                                      (uint32_t)e->c.hidden_size};
-            void* sh = e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr;
-            for (int k = 0; k < (e->one_sweep ? 1 : all.count); ++k) {
-                AdamRanges one = all;
-                if (!e->one_sweep) { one = AdamRanges{}; one.begin[0] = all.begin[k]; one.n[0] = all.n[k]; one.slot[0] = all.slot[k]; one.count = 1; }
-                CK(adamw_sweep(e->P, e->G, m, v, sh, one, nd, e->sh_begin, e->sh_end, keep ? e->stale_begin : 0, keep ? e->stale_end : 0,
-                               e->adam_state(ws), ws_, st));
-            }
-            CK(e->prof_mark(2 * NL + 1, st));
-            return MB_OK;
-        }
-        if (ride) CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));       // what no launch carried (layer 0 always)
-        CK(adamw_decay_range(e, m, v, ride ? e->wp : 0, nd, st));
-        CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
-        CK(e->prof_mark(2 * NL + 1, st));
-    }
+    if (m && v) CK(enqueue_update(e, m, v, ride, clip, st));      // (dp_step.h: clip, statistics, the sweep of what the riders left)
     return MB_OK;
 }
 

@@ -270,6 +270,9 @@ struct StepMixin {
     size_t skip_updates = 0;       // updates enqueued with the proof in hand (mb_*_word_skip_updates: what the tests look at)
     uint32_t* stamp_table(char* ws) const { return (uint32_t*)(ws + stamp_off); }
     uint32_t* stamp_state(char* ws) const { return stamp_table(ws) + stamp_rows; }
+    // the unclassed end-of-step sweep as ONE launch over its up-to-three ranges (dp_step.h enqueue_update); false: one launch per range.
+    // MAG-BERT: MB_ADAMW_ONE_SWEEP (default on); MAG-XLNet keeps its separate launches
+    bool one_sweep = false;
     bool loss_cleared = false;     // single-call step: the step prologue clears the loss accumulator (no zero_fill launch in the forward)
     bool capturing = false;        // the stream is in capture mode: nothing outside the captured sequence may be waited for
     int nsites = 0;
@@ -587,6 +590,11 @@ struct StepMixin {
         for (const auto& u : frz_unwritten) if (u.first <= b && e <= u.second) return true;
         return false;
     }
+    // a single-call step is about to enqueue its backward: nothing noted, hopped or skipped yet (the engine's note_unwritten calls follow)
+    void begin_step_marks() {
+        frz_unwritten.clear(); ride_hopped = 0; frz_wgrad_skipped = frz_embed_skipped = 0;
+        frz_elems = any_frozen ? frozen_total() : 0;
+    }
     void note_unwritten(size_t b, size_t e) {
         if (e <= b) return;
         if (!frz_unwritten.empty() && frz_unwritten.back().second == b) frz_unwritten.back().second = e;
@@ -630,20 +638,29 @@ struct StepMixin {
         }
         return false;
     }
-    // the sweep of a classed step: [b0, e0) and [b1, e1) (ascending, disjoint) cut at the segment boundaries
-    // A frozen segment gets no update piece.  clear: what the step's backward wrote of it (everything but frz_unwritten and the keep range
-    // [keep_b, keep_e), which stays "logically zero, physically stale" like its trainable neighbours) gets clear-only pieces, which lie
-    // behind every update piece of the table (kernels.h AdamPieces::clear_first).
+    // the sweep of a classed step: [b0, e0) and [b1, e1) (ascending, disjoint) cut at the segment boundaries, every piece with its
+    // segment's slot of the class table
     int sweep_pieces(AdamPieces& out, size_t b0, size_t e0, size_t b1, size_t e1, bool clear = true, size_t keep_b = 0, size_t keep_e = 0) const {
+        std::vector<int> slots(seg_class.size());
+        for (size_t s = 0; s < slots.size(); ++s) slots[s] = seg_slot(s);
+        return cut_pieces(out, seg_bounds, slots.data(), seg_frozen.empty() ? nullptr : seg_frozen.data(), b0, e0, b1, e1, clear, keep_b, keep_e);
+    }
+    // The piece table of a sweep (kernels.h AdamPieces): [b0, e0) and [b1, e1) (ascending, disjoint) cut at `bounds`, the part inside
+    // [bounds[s], bounds[s + 1]) with slot[s].  An unclassed step cuts at {0, n_decay, n} with slots {0, 1} of adam_state.
+    // frozen (null: none): a frozen segment gets no update piece.  clear: what the step's backward wrote of it (everything but
+    // frz_unwritten and the keep range [keep_b, keep_e), which stays "logically zero, physically stale" like its trainable neighbours)
+    // gets clear-only pieces, which lie behind every update piece of the table (kernels.h AdamPieces::clear_first).
+    int cut_pieces(AdamPieces& out, const std::vector<size_t>& bounds, const int* slot, const uint8_t* frozen, size_t b0, size_t e0, size_t b1,
+                   size_t e1, bool clear = true, size_t keep_b = 0, size_t keep_e = 0) const {
         out = AdamPieces{};
         const size_t rb[2] = {b0, b1}, re[2] = {e0, e1};
         struct Piece { size_t lo, hi; int slot; };
         std::vector<Piece> upd, clr;
         for (int r = 0; r < 2; ++r)
-            for (size_t s = 0; s + 1 < seg_bounds.size(); ++s) {
-                const size_t lo = std::max(rb[r], seg_bounds[s]), hi = std::min(re[r], seg_bounds[s + 1]);
+            for (size_t s = 0; s + 1 < bounds.size(); ++s) {
+                const size_t lo = std::max(rb[r], bounds[s]), hi = std::min(re[r], bounds[s + 1]);
                 if (lo >= hi) continue;
-                if (seg_frozen.empty() || !seg_frozen[s]) { upd.push_back({lo, hi, seg_slot(s)}); continue; }
+                if (!frozen || !frozen[s]) { upd.push_back({lo, hi, slot[s]}); continue; }
                 if (!clear) continue;
                 // [lo, hi) minus the ranges nobody wrote
                 std::vector<std::pair<size_t, size_t>> holes = frz_unwritten;

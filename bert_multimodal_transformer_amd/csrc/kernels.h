@@ -291,26 +291,24 @@ int head_backward(int dtype, const float* dlogits, const float* logits, const fl
 int adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, size_t n_decay,
                size_t sh_begin, size_t sh_end, AdamArgs a, int zero_grad, hipStream_t st, const AdamArgs* dyn = nullptr,
                size_t keep_begin = 0, size_t keep_end = 0);
-// The end-of-step sweep of a single-call step as ONE launch over a short list of ranges of the flat buffers (three launches otherwise:
-// what the riders left of the layers, the rest of the decay slab, the no-decay slab).  Everything is ABSOLUTE here: p / g / m / v /
-// shadow are the buffers' first elements; ranges, n_decay, the shadow and keep ranges are element offsets (multiples of 4) into them;
-// range k reads its scalars from dyn[slot[k]].  Same per-element arithmetic as adamw_step (adam_update_store): the same bits.
-#define MB_SWEEP_MAX 4
-struct AdamRanges { size_t begin[MB_SWEEP_MAX], n[MB_SWEEP_MAX]; int slot[MB_SWEEP_MAX]; int count; };
 // Word-embedding rows the step did not touch (MB_ADAMW_SKIP_ZERO_ROWS): stamp[row] == state[0] <=> the prologue of a step whose
 // backward feeds this update saw `row` in its batch (PrologueArgs::stamp).  When state[1] != 0 the engine vouches that every other row
 // of [begin, end) -- rows of `row_len` elements -- holds g == +0.0f: the sweep neither loads that gradient nor stores the zero back,
 // and runs the same arithmetic on a +0.0f it makes up.  state[1] == 0: the full read (decided per step, so a replayed graph obeys it).
 struct WordSkip { const uint32_t* stamp; const uint32_t* state; size_t begin, end; uint32_t row_len; };
-int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const AdamRanges& r, size_t n_decay, size_t sh_begin, size_t sh_end,
-                size_t keep_begin, size_t keep_end, const AdamArgs* dyn, const WordSkip& skip, hipStream_t st);
+// The end-of-step sweep of a single-call step as ONE launch over a table of pieces of the flat buffers (one adamw_step per range
+// otherwise).  Everything is ABSOLUTE here: p / g / m / v / shadow are the buffers' first elements, the shadow and keep ranges element
+// offsets (multiples of 4) into them.  Piece k covers quads [begin4[k], begin4[k] + start4[k + 1] - start4[k]) of the buffers, start4
+// being the running sum of the pieces' lengths, and reads its scalars from cls[slot[k]]; that slot's own weight_decay decides whether
+// the piece decays (no n_decay here).  Same per-element arithmetic as adamw_step (adam_update_store): the same bits.
+// `cls` is any table of AdamArgs.  An unclassed step hands over its two scalars (engine_common.h adam_state: slot 0 = the decay slab,
+// slot 1 = the same scalars with weight_decay 0) and up to three pieces: what the riders left of the layers, the rest of the decay
+// slab, the no-decay slab.
 // Update classes (include/magbert_hip.h: mb_*_set_update_map): one optimizer parameter group's scalars per slot of a table in device
-// memory, and the flat layout cut into segments -- maximal runs of tensors of one class.  The sweep of a classed step is ONE launch over
-// a table of pieces (what the riders left, cut at the segment boundaries): piece k covers quads [begin4[k], begin4[k] + start4[k + 1] -
-// start4[k]) of the buffers, start4 being the running sum of the pieces' lengths, and reads its scalars from cls[slot[k]].  The class's
-// own weight_decay decides whether a piece decays (no n_decay here).  Same per-element arithmetic as adamw_sweep: the same bits.
-// The table has two halves of MB_CLASSES_MAX slots: slot MB_CLASSES_MAX + c is class c with weight_decay = 0, for segments marked
-// no-decay (mb_*_set_update_decay) -- the pieces and riders of such a segment name that slot, and no kernel knows about marks.
+// memory, and the flat layout cut into segments -- maximal runs of tensors of one class; the pieces are the same ranges cut at the
+// segment boundaries.  That table has two halves of MB_CLASSES_MAX slots: slot MB_CLASSES_MAX + c is class c with weight_decay = 0,
+// for segments marked no-decay (mb_*_set_update_decay) -- the pieces and riders of such a segment name that slot, and no kernel knows
+// about marks.
 #define MB_CLASSES_MAX 32
 #define MB_SEGMENTS_MAX 128
 #define MB_SWEEP_PIECES_MAX (MB_SEGMENTS_MAX + 2)
@@ -320,8 +318,8 @@ int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const Adam
 // through both), and extra blocks of the same launch take them.
 #define MB_PIECE_CLEAR 0xff
 struct AdamPieces { uint32_t begin4[MB_SWEEP_PIECES_MAX], start4[MB_SWEEP_PIECES_MAX + 1]; uint8_t slot[MB_SWEEP_PIECES_MAX]; int count, clear_first; };
-int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
-                        size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st);
+int adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, const AdamPieces& r, size_t sh_begin, size_t sh_end,
+                size_t keep_begin, size_t keep_end, const AdamArgs* cls, const WordSkip& skip, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------ gradient-norm clipping (gradnorm.hip)
 // grad_sumsq: partial[b] = the sum over block b's share of g[0, n) of (double)g[i]^2, b < grad_norm_blocks(n) (<= 2048, a function of n
@@ -332,7 +330,7 @@ int adamw_sweep_classed(float* p, float* g, float* m, float* v, void* shadow, co
 // pointer, may be null): {max_norm, grad_scale} are read from there instead (replayed step graphs: PrologueArgs::clip).
 unsigned grad_norm_blocks(size_t n);
 int grad_sumsq(const float* g, size_t n, double* partial, hipStream_t st);
-// grad_sumsq_pieces: the same sum over the pieces of `r` only (begin4 / start4 as the classed sweep reads them, slots ignored): a step that
+// grad_sumsq_pieces: the same sum over the pieces of `r` only (begin4 / start4 as the sweep reads them, slots ignored): a step that
 // freezes segments takes the norm of the trainable ranges.  The pieces laid end to end are cut into one contiguous share per block on the
 // host's layout alone (blocks = grad_norm_blocks(4 * start4[count])), every block adds its share in index order: the same bits on every run.
 int grad_sumsq_pieces(const float* g, const AdamPieces& r, double* partial, unsigned* blocks, hipStream_t st);

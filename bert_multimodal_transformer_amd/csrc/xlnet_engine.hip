@@ -35,6 +35,7 @@ struct mb_xlnet_engine : StepMixin {
     size_t layer_begin(int l) const { return lo[l].q; }
     size_t layers_end() const { return wsum; }
     int width() const { return c.d_model; }
+    WordSkip word_skip(char*) const { return {}; }          // (dp_step.h enqueue_update: this engine stamps no word rows)
     MagWs mw;
     size_t ws_mag, ws_magout, ws_pos, ws_xs, ws_head_z, ws_head_pooled;
     std::vector<size_t> ws_x;
@@ -634,8 +635,7 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
     e->ride_m = ride ? m : nullptr; e->ride_v = ride ? v : nullptr;
     e->ride_cursor = e->wsum;
     // frozen marks: what this step's backward will not write (StepMixin::frz_unwritten): the GEMM weights of fully frozen layers, a frozen word table
-    e->frz_unwritten.clear(); e->ride_hopped = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
-    e->frz_elems = e->any_frozen ? e->frozen_total() : 0;
+    e->begin_step_marks();
     if (e->skipping()) {
         for (int l = 0; l < e->c.n_layer; ++l) if (e->range_frozen(e->lo[l].q, e->layer_end(l))) e->note_unwritten(e->lo[l].q, e->layer_end(l));
         const size_t word_end = e->word + (size_t)e->c.vocab_size * e->c.d_model;
@@ -644,40 +644,8 @@ static int xl_enqueue_step(mb_xlnet_engine* e, int B, int L, float* logits, floa
     const int rb = mb_xlnet_backward(e, nullptr, lab, loss_scale, 0, e->c.n_layer + 2, st);
     e->ride_m = e->ride_v = nullptr;
     CK(rb);
-    if (clip) CK(e->enqueue_clip(e->G, e->n_trainable, ws, st));      // the whole gradient is final: its norm, the coefficient into the sweep's scalars
-    if (m && v) {
-        e->upd_ridden = ride ? e->wsum - e->ride_cursor - e->ride_hopped : 0; e->upd_swept = e->n_trainable - e->upd_ridden - e->frz_elems;
-        e->upd_segments = e->n_classes > 0 ? (int)e->seg_class.size() : 0;
-    }
-    if (m && v && e->n_classes > 0) {
-        // Classed step (kernels.h AdamPieces): what the riders left and the rest of both slabs, cut at the segment boundaries, every piece
-        // with its class's slot, as ONE launch
-        AdamPieces pieces;
-        const bool keep = e->keep_in_step();
-        CK(e->sweep_pieces(pieces, 0, ride ? e->ride_cursor : e->wsum, e->wsum, e->n_trainable, true, keep ? e->stale_begin : 0, keep ? e->stale_end : 0));
-        CK(e->prof_mark(2 * e->c.n_layer, st));
-        CK(adamw_sweep_classed(e->P, e->G, m, v, e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr, pieces, e->sh_begin, e->sh_end,
-                               keep ? e->stale_begin : 0, keep ? e->stale_end : 0, e->class_state(ws), WordSkip{}, st));
-        CK(e->prof_mark(2 * e->c.n_layer + 1, st));
-    } else if (m && v && ride) {
-        const AdamArgs none = {};
-        const size_t nd = e->n_decay, n = e->n_trainable;
-        CK(e->prof_mark(2 * e->c.n_layer, st));
-        CK(adamw_decay_range(e, m, v, 0, e->ride_cursor, st));          // what no launch carried (layer 0 always)
-        CK(adamw_decay_range(e, m, v, e->wsum, nd, st));
-        CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
-        CK(e->prof_mark(2 * e->c.n_layer + 1, st));
-    } else if (m && v) {
-        const AdamArgs none = {};
-        const size_t nd = e->n_decay, n = e->n_trainable;        // the frozen mask_emb slot behind n_trainable is never updated
-        void* sh = e->c.dtype == DT_BF16 ? (void*)e->SH : nullptr;
-        const bool keep = e->keep_in_step();          // the layers' GEMM weight gradients: overwritten by the next backward, not zeroed
-        CK(e->prof_mark(2 * e->c.n_layer, st));
-        CK(adamw_step(e->P, e->G, m, v, sh, nd, nd, e->sh_begin, e->sh_end, none, 1, st, e->adam_state(ws), keep ? e->stale_begin : 0,
-                      keep ? e->stale_end : 0));
-        CK(adamw_step(e->P + nd, e->G + nd, m + nd, v + nd, nullptr, n - nd, 0, 0, 0, none, 1, st, e->adam_state(ws) + 1));
-        CK(e->prof_mark(2 * e->c.n_layer + 1, st));
-    }
+    // (dp_step.h: clip, statistics, the sweep of what the riders left -- the frozen mask_emb slot behind n_trainable is never updated)
+    if (m && v) CK(enqueue_update(e, m, v, ride, clip, st));
     return MB_OK;
 }
 

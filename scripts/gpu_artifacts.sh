@@ -45,7 +45,7 @@ timeout 60 tools/bin/launch_floor > $O/launch_floor.txt 2>&1
 [ -f gpurun_ab/looptrace/libmagbert_hip.so ] && LD_LIBRARY_PATH=$R/gpurun_ab/looptrace:$LD_LIBRARY_PATH MB_GEMM_TRACE=1 timeout 120 tools/bin/gemm_bench --looptrace 1 > $O/gemm_looptrace.txt 2>&1
 # same-box A/B of the software-pipelined k loop against the plain loop (-DMB_GEMM_PLAIN_LOOP build, if present)
 [ -f gpurun_ab/plainloop/libmagbert_hip.so ] && REPS=2 bash scripts/gpu_ab.sh plainloop > $O/ab_pipelined_vs_plain.txt 2>&1
-{ timeout 60 tools/bin/adamw_bench; MB_ADAMW_VAR=0 timeout 60 tools/bin/adamw_bench; timeout 60 tools/bin/adamw_bench --zero 0; } > $O/adamw_bench.txt 2>&1
+{ timeout 60 tools/bin/adamw_bench; timeout 60 tools/bin/adamw_bench --zero 0; } > $O/adamw_bench.txt 2>&1
 # clocks / power while the step runs (sustained load: what the in-step kernel durations are measured at)
 { timeout 60 $SB --graph 1 --h2d 2 --steps 3000 --warmup 10 > $O/clocks_step.txt 2>&1 & SBPID=$!
   sleep 4; for k in 1 2 3; do timeout 10 rocm-smi --showclocks --showpower 2>&1 | grep -E "sclk|mclk|fclk|Power|power" ; echo --; sleep 2; done; wait $SBPID; cat $O/clocks_step.txt; } > $O/clocks_under_load.txt 2>&1

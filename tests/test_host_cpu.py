@@ -570,18 +570,15 @@ def test_bench_refuses_to_run_fewer_ranks_than_asked(monkeypatch):
     assert "only 4 device(s) visible" in str(ex.value) and ex.value.code not in (0, None)
 
 
-def test_rider_branches_do_not_cost_a_gemm_kernel_its_residency(tmp_path):
-    """kernels.h AdamRide: the rider branch (an AdamW update with several quads in flight) sits inside GEMM kernels, and registers are
-    allocated for the larger of a kernel's branches.  Round 6 found it had silently taken the 64 x 64 dgrad kernel from three blocks per
-    CU to two (200 registers: a second round of tiles, +3.7 us per launch) and MAG's 64 x 64 grouped kernels from 48-72 registers to
-    ~200.  Checked on the code-object metadata of the objects build() produced: blocks per CU by registers >= blocks per CU by LDS."""
+def _code_object_kernels(tmp_path, obj_name):
+    """{kernel name: (vgpr_count, group_segment_fixed_size, vgpr_spill_count)} from the gfx950 code-object notes of an object build() produced."""
     import shutil
     from bert_multimodal_transformer_amd import build as mb_build
     mb_build.build(verbose=False)
     objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
     if not (os.path.exists(objdump) and os.path.exists(readelf)):
         pytest.skip("llvm-objdump / llvm-readelf not in this image")
-    obj = shutil.copy(os.path.join(mb_build.LIBDIR, "obj", "gemm.o"), tmp_path / "gemm.o")
+    obj = shutil.copy(os.path.join(mb_build.LIBDIR, "obj", obj_name), tmp_path / obj_name)
     subprocess.run([objdump, "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
     dev = [f for f in os.listdir(tmp_path) if "gfx950" in f]
     notes = subprocess.run([readelf, "--notes", str(tmp_path / dev[0])], check=True, capture_output=True, text=True).stdout
@@ -593,7 +590,19 @@ def test_rider_branches_do_not_cost_a_gemm_kernel_its_residency(tmp_path):
             if m.group(1) == "wavefront_size":
                 kernels[cur["name"]] = (int(cur["vgpr_count"]), int(cur["group_segment_fixed_size"]), int(cur.get("vgpr_spill_count", 0)))
                 cur = {}
-    by_reg = lambda v: 512 // ((v + 7) // 8 * 8)           # waves per SIMD = 256-thread blocks per CU
+    return kernels
+
+
+_waves_by_reg = lambda v: 512 // ((v + 7) // 8 * 8)           # waves per SIMD = 256-thread blocks per CU
+
+
+def test_rider_branches_do_not_cost_a_gemm_kernel_its_residency(tmp_path):
+    """kernels.h AdamRide: the rider branch (an AdamW update with several quads in flight) sits inside GEMM kernels, and registers are
+    allocated for the larger of a kernel's branches.  Round 6 found it had silently taken the 64 x 64 dgrad kernel from three blocks per
+    CU to two (200 registers: a second round of tiles, +3.7 us per launch) and MAG's 64 x 64 grouped kernels from 48-72 registers to
+    ~200.  Checked on the code-object metadata of the objects build() produced: blocks per CU by registers >= blocks per CU by LDS."""
+    kernels = _code_object_kernels(tmp_path, "gemm.o")
+    by_reg = _waves_by_reg
     by_lds = lambda l: (160 * 1024) // l
     checked = 0
     for name, (vgpr, lds, spill) in kernels.items():
@@ -604,3 +613,18 @@ def test_rider_branches_do_not_cost_a_gemm_kernel_its_residency(tmp_path):
     # the layers' grouped kernels carry riders and stay at two blocks per CU (64 KB of LDS each)
     g128 = [v for n, v in kernels.items() if "gemm2_grouped_tn_kernelIDF16bLi128ELi128ELi2ELi128E" in n]
     assert g128 and by_reg(g128[0][0]) >= 2 and g128[0][2] == 0, g128
+
+
+def test_adamw_kernels_keep_their_residency(tmp_path):
+    """adamw.hip is five kernels around one update loop (adamw_dev.h adam_span): the single-range kernel and the sweep, each with and
+    without non-temporal accesses, and the scalar tail.  The loop is HBM-bound and lives on resident waves: the single-range kernel
+    keeps 8 waves per SIMD (62 VGPRs) and the sweep 7 (66 VGPRs; 68 before the loop was shared), and nothing spills."""
+    kernels = {n: k for n, k in _code_object_kernels(tmp_path, "adamw.o").items() if "adamw" in n}
+    single = [k for n, k in kernels.items() if "adamw_range_kernel" in n]
+    sweep = [k for n, k in kernels.items() if "adamw_sweep_kernel" in n]
+    tail = [k for n, k in kernels.items() if "adamw_tail_kernel" in n]
+    print({n: (v, _waves_by_reg(v), s) for n, (v, _, s) in kernels.items()})
+    assert len(kernels) == 5 and len(single) == 2 and len(sweep) == 2 and len(tail) == 1, sorted(kernels)
+    assert all(spill == 0 for _, _, spill in kernels.values()), kernels
+    assert all(_waves_by_reg(v) >= 8 for v, _, _ in single), single
+    assert all(_waves_by_reg(v) >= 7 for v, _, _ in sweep), sweep

@@ -1,5 +1,5 @@
 """GPU: the end-of-step AdamW sweep of the single-call MAG-BERT step as ONE launch over its ranges (MB_ADAMW_ONE_SWEEP, csrc/kernels.h
-AdamRanges) that leaves alone the gradient of word-embedding rows no batch of the update touched (MB_ADAMW_SKIP_ZERO_ROWS, csrc/kernels.h
+AdamPieces) that leaves alone the gradient of word-embedding rows no batch of the update touched (MB_ADAMW_SKIP_ZERO_ROWS, csrc/kernels.h
 WordSkip, csrc/engine_common.h StepMixin::stamp_live).
 
 Same per-element arithmetic on a +0.0f the kernel makes up instead of the +0.0f it would have loaded, so nothing may change: in
@@ -49,14 +49,14 @@ def _dev(b):
     return t("input_ids"), t("visual"), t("acoustic"), t("input_mask"), t("segment_ids"), t("label_ids")
 
 
-def _run(monkeypatch, cdt, on, batches, accum=1, mode=True, unfused=()):
+def _run(monkeypatch, cdt, on, batches, accum=1, mode=True, unfused=(), one_sweep=None):
     """len(batches) / accum optimizer updates (dropout on, schedule moving) through model.train_step.  mode: True = prologue + replayed
     graph (mode 1), 2 = prologue + the same launches one by one; unfused: indices of the updates taken through training_step +
-    optimizer.step() instead (accum == 1 only)."""
+    optimizer.step() instead (accum == 1 only).  on: MB_ADAMW_SKIP_ZERO_ROWS, and MB_ADAMW_ONE_SWEEP too unless one_sweep says otherwise."""
     from bert_multimodal_transformer_amd.multimodal_driver import optimizer_grouped_parameters
     monkeypatch.setenv("MB_DETERMINISTIC", "1")
     monkeypatch.setenv("MB_ADAMW_SKIP_ZERO_ROWS", "1" if on else "0")
-    monkeypatch.setenv("MB_ADAMW_ONE_SWEEP", "1" if on else "0")
+    monkeypatch.setenv("MB_ADAMW_ONE_SWEEP", "1" if (on if one_sweep is None else one_sweep) else "0")
     torch.manual_seed(77)
     m = _build(cdt).train()
     opt = AdamW(optimizer_grouped_parameters(m), lr=1e-3)
@@ -108,6 +108,16 @@ def test_one_sweep_that_skips_untouched_word_rows_changes_nothing(cdt, monkeypat
     _same(on, off, "switches on vs off")
     assert on["stats"] == off["stats"] and on["stats"][0] == 3 and on["stats"][1] == 4, (on["stats"], off["stats"])
     assert off["skipped"] == 0 and on["skipped"] == 3, (off["skipped"], on["skipped"])
+
+
+def test_the_skip_with_one_launch_per_range_changes_nothing(monkeypatch):
+    """MB_ADAMW_SKIP_ZERO_ROWS=1 with MB_ADAMW_ONE_SWEEP=0: one launch per range, each a one-piece table of the sweep kernel, against
+    both switches off (adamw_step per range).  Three updates; the first never skips."""
+    batches = [_batch(B, L, 590 + s) for s, (B, L) in enumerate(((24, 50), (5, 40), (24, 50)))]
+    off = _run(monkeypatch, torch.bfloat16, False, batches)
+    on = _run(monkeypatch, torch.bfloat16, True, batches, one_sweep=False)
+    _same(on, off, "skip on with one launch per range vs both switches off")
+    assert off["skipped"] == 0 and on["skipped"] == 2, (off["skipped"], on["skipped"])
 
 
 def test_rows_touched_by_an_earlier_micro_step_only_are_not_skipped(monkeypatch):
