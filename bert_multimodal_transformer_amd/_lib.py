@@ -78,6 +78,13 @@ PROTOTYPES = {
     "mb_bert_pooled_output": (_vp, [_vp]),
     "mb_bert_hidden_state": (_vp, [_vp, _i]),
     "mb_bert_set_attention_output": (_i, [_vp, _vp]),
+    # test hooks (tests/gemm_op_helpers.py): what mb_gemm / mb_gemm_grouped_wgrad cannot set, and which kernel the last launch used
+    "mb_debug_gemm_ex": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _dk, _i, _i,
+                              _i, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _f, _f, _f, _f, _f, _i, _i, _f, _vp,
+                              C.POINTER(_i), _vp]),
+    "mb_debug_gemm_grouped_ex": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                      _sz, _i, _i, _f, _f, _f, _f, _f, _i, _i, _f, _vp, _vp]),
+    "mb_debug_gemm_last_kernel": (_i, [C.c_char_p, _i]),
     "mb_debug_gemm_trace": (_i, [_vp, _i]),
     "mb_debug_attention_trace": (_i, [_vp, _i]),
     "mb_xlnet_attention_probs": (_vp, [_vp, _i, C.POINTER(_i)]),

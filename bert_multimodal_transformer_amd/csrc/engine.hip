@@ -236,6 +236,30 @@ static int prepare_pass(mb_bert_engine* e, int T, hipStream_t st) {
     return MB_OK;
 }
 
+// the scalars of one HF-AdamW step (mb_adamw_step, and the riders of the mb_debug_gemm*_ex test hooks)
+static AdamArgs adam_scalars(float lr, float beta1, float beta2, float eps, float weight_decay, int step, int correct_bias, float grad_scale) {
+    AdamArgs a;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
+    double ss = lr;
+    if (correct_bias) ss = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+    a.step_size = (float)ss;
+    return a;
+}
+// Test hooks: the rider of a mb_debug_gemm*_ex call.  `adam_dev` (device memory, sizeof(AdamArgs)) receives the step's scalars before the
+// launch -- a rider reads them from device memory, as inside a replayed step.  blocks == 0: no rider.
+static int debug_ride(AdamRide& r, float* p, float* g, float* m, float* v, void* shadow, size_t n4, int blocks, int zero_grad, const AdamArgs& a,
+                      void* adam_dev, hipStream_t st) {
+    r = AdamRide{};
+    if (blocks == 0) return MB_OK;
+    if (blocks < 0 || !p || !g || !m || !v || !adam_dev) return MB_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)shadow & 7) || ((uintptr_t)adam_dev & 3)) return MB_ERR_SHAPE;
+    CK((int)hipMemcpyAsync(adam_dev, &a, sizeof(AdamArgs), hipMemcpyHostToDevice, st));
+    CK((int)hipStreamSynchronize(st));       // (`a` is the caller's stack)
+    r.p = p; r.g = g; r.m = m; r.v = v; r.shadow = (bf16*)shadow; r.n4 = n4; r.dyn = (const AdamArgs*)adam_dev; r.blocks = blocks;
+    r.zero_grad = zero_grad;
+    return MB_OK;
+}
+
 extern "C" {
 
 const char* mb_error_string(int code) {
@@ -266,6 +290,62 @@ int mb_gemm(int dtype, int layout, int epilogue, int M, int N, int K, const void
     if (epilogue == EPI_DGELU) { a.colsum = Cf; a.Cf = nullptr; }       // epilogue 4: the fp32 pointer is the fused bias gradient
     return gemm_launch(dtype, layout, epilogue, a, splits, tile, (hipStream_t)stream);
 }
+
+int mb_debug_gemm_ex(int dtype, int layout, int epilogue, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                     void* C, int ldc, void* C2, float* Cf, const float* bias, const void* R, int ldr, float alpha,
+                     const mb_dropkey* drop, int splits, int tile, int bseg, size_t bseg_stride, int cvalid, int overwrite,
+                     long long* colsum_shadow, int fold, float* rp, float* rg, float* rm, float* rv, void* rshadow, size_t n4, int blocks,
+                     int zero_grad, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int correct_bias,
+                     float grad_scale, void* adam_dev, int* ride_tiles, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs a = {};
+    a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.C = C; a.ldc = ldc; a.C2 = C2; a.Cf = Cf;
+    a.bias = bias; a.R = R; a.ldr = ldr; a.alpha = alpha; a.drop = dk(drop); a.kchunk = K; a.colsum = nullptr;
+    if (epilogue == EPI_DGELU) { a.colsum = Cf; a.Cf = nullptr; }
+    a.bseg = bseg; a.bseg_stride = bseg_stride; a.cvalid = cvalid; a.overwrite = overwrite;
+    if (colsum_shadow) {
+        if (!a.colsum) return MB_ERR_ARG;
+        a.acc = GradAcc{colsum_shadow, a.colsum};
+    }
+    if (ride_tiles) *ride_tiles = 0;
+    AdamRide ride;
+    if (int e = debug_ride(ride, rp, rg, rm, rv, rshadow, n4, blocks, zero_grad,
+                           adam_scalars(lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale), adam_dev, st)) return e;
+    if (ride.blocks > 0) {
+        if (layout != GEMM_NN || splits > 1 || tile != 0) return MB_ERR_MODE;
+        int per_cu = 0;
+        const int tiles = gemm_nn_ride_tiles(dtype, epilogue, a, &per_cu);
+        if (ride_tiles) *ride_tiles = tiles;
+        CK(gemm_nn_ride_launch(dtype, epilogue, a, ride, st));
+    } else {
+        CK(gemm_launch(dtype, layout, epilogue, a, splits, tile, st));
+    }
+    if (colsum_shadow && fold) CK(grad_fold(a.acc, a.colsum, 0, (size_t)N, st));
+    return MB_OK;
+}
+
+int mb_debug_gemm_grouped_ex(int dtype, int count, const int* M, const int* N, int K, const void* const* dY, const int* ldy,
+                             const void* const* X, const int* ldx, float* const* dW, const int* ldw, const int* cvalid,
+                             const int* overwrite, int tile, int stages, float* rp, float* rg, float* rm, float* rv, void* rshadow,
+                             size_t n4, int blocks, int zero_grad, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int step, int correct_bias, float grad_scale, void* adam_dev, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (count < 1 || count > MB_MAX_GROUP || !M || !N || !dY || !X || !dW || !ldy || !ldx || !ldw) return MB_ERR_ARG;
+    if (stages != 0 && stages != 4 && stages != 5) return MB_ERR_ARG;
+    GemmArgs g[MB_MAX_GROUP];
+    for (int i = 0; i < count; ++i) {
+        g[i] = wgrad_args(M[i], N[i], K, dY[i], ldy[i], X[i], ldx[i], dW[i], ldw[i]);
+        g[i].cvalid = cvalid ? cvalid[i] : 0;
+        g[i].overwrite = overwrite ? overwrite[i] : 0;
+    }
+    if (!gemm_grouped_tn_ok(dtype, g, count, tile)) return MB_ERR_SHAPE;
+    AdamRide ride;
+    if (int e = debug_ride(ride, rp, rg, rm, rv, rshadow, n4, blocks, zero_grad,
+                           adam_scalars(lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale), adam_dev, st)) return e;
+    return gemm_grouped_tn_launch(dtype, g, count, tile, st, stages, ride.blocks > 0 ? &ride : nullptr);
+}
+
+int mb_debug_gemm_last_kernel(char* out, int cap) { return gemm_last_kernel(out, cap); }
 
 int mb_debug_gemm_trace(unsigned long long* host_out, int max_blocks) { return gemm_trace_fetch(host_out, max_blocks); }
 int mb_debug_attention_trace(unsigned long long* host_out, int max_blocks) { return attention_trace_fetch(host_out, max_blocks); }
@@ -396,11 +476,7 @@ int mb_mag_backward(int dtype, const void* d_out, const void* text, const float*
 int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, size_t n_decay, size_t sh_begin,
                   size_t sh_end, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   int correct_bias, float grad_scale, int zero_grad, void* stream) {
-    AdamArgs a;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
-    double ss = lr;
-    if (correct_bias) ss = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-    a.step_size = (float)ss;
+    const AdamArgs a = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale);
     return adamw_step(p, g, m, v, shadow, n, n_decay, sh_begin, sh_end, a, zero_grad, (hipStream_t)stream);
 }
 

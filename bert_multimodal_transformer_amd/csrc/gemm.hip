@@ -19,6 +19,7 @@
 //
 // The accumulator is computed transposed (mma16(acc, Bfrag, Afrag)) so that a lane owns 4 CONSECUTIVE
 // columns n of one row m: epilogue loads/stores are 8/16-byte vectors and bias is one float4.
+#include <cstring>
 #include "gemm_tile.h"
 #include "adamw_dev.h"
 
@@ -628,7 +629,21 @@ static const HostEnv& host_env() {
     return e;
 }
 
+// the kernel of this process's last GEMM launch (test hook mb_debug_gemm_last_kernel): one pointer store per launch, whatever MB_GEMM_LOG
+// says; the symbol is looked up when somebody asks
+static const void* g_last_kernel = nullptr;
+int gemm_last_kernel(char* out, int cap) {
+    if (!out || cap < 1) return 0;
+    out[0] = 0;
+    if (!g_last_kernel) return 0;
+    const char* name = hipKernelNameRefByPtr(g_last_kernel, nullptr);
+    if (!name) return 0;
+    snprintf(out, (size_t)cap, "%s", name);
+    return (int)strlen(out);
+}
+
 void gemm_log(const void* fn, hipStream_t st, const GemmArgs* p, int count) {
+    g_last_kernel = fn;
     if (!host_env().log) return;
     double fl = 0.0;
     for (int i = 0; i < count; ++i) fl += 2.0 * (double)p[i].M * (double)p[i].N * (double)p[i].K;
@@ -720,8 +735,10 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t st) {
         if (env.stages > 0) { kb = (env.stages / 10 == 2) ? 64 : 128; ns = env.stages % 10; }
         if (kb == 64 && (p.kchunk % (64 / (int)sizeof(T)) != 0)) kb = 128;
         // the two-slot bf16 loop is a software pipeline with its last two stages peeled: a k range of a single stage takes the
-        // three-slot kernel (plain loop)
-        if (sizeof(T) == 2 && ns <= 2 && p.kchunk / (kb / (int)sizeof(T)) < 2) ns = 3;
+        // three-slot kernel (plain loop).  With split-K that holds for the LAST chunk too, which is what K leaves over: K = 5 stages in
+        // 3 splits is 2 + 2 + 1, and the pipelined loop would request and multiply a second stage behind the operands' last k row
+        const int klast = p.K - (splits - 1) * p.kchunk;
+        if (sizeof(T) == 2 && ns <= 2 && std::min(p.kchunk, klast) / (kb / (int)sizeof(T)) < 2) ns = 3;
 #define MB_LAUNCH2(NS, KBV) MB_GEMM_LAUNCH((gemm2_kernel<T, BM, BN, AK, BK, MODE, NS, KBV>), grid, dim3(256), st, p, &p, 1)
         if constexpr (BM == 64 && BN == 64 && sizeof(T) == 2) {
             // each k-split block holds 64 KB of LDS (2 per CU): worth it while the whole grid is co-resident and the k loop is long
@@ -877,6 +894,9 @@ static int launch_tile(const GemmArgs& a, int splits, int tile, hipStream_t st) 
     if (tile == 256) tile = 128;
     if (tile == 128) return launch_cfg<T, 128, 128, AK, BK, MODE>(a, splits, st);
     if (tile == 12864) return launch_cfg<T, 128, 64, AK, BK, MODE>(a, splits, st);
+    // a caller that NAMES one of the narrow ping-pong tiles for a segmented B is refused: those kernels take none, and a named tile that
+    // quietly ran 64 x 64 would hide that (the auto selection, tile 0, still takes segmented problems to 64 x 64)
+    if (forced && (tile == 12872 || tile == 25672) && a.bseg > 0) return MB_ERR_SHAPE;
     if (tile == 12872) return launch_pn<T, AK, BK, MODE>(a, splits, forced, st, forced ? 0 : -1);      // (falls back to 64 x 64 by itself)
     if (tile == 25672) return launch_pn<T, AK, BK, MODE>(a, splits, forced, st, 1);                    // the 256 x 64 form by name
     return launch_cfg<T, 64, 64, AK, BK, MODE>(a, splits, st);

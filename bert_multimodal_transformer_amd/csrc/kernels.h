@@ -69,6 +69,8 @@ struct GemmArgs {
 };
 // copies the stamps of the last traced launch to the host (measurement tooling: tools/gemm_bench --trace); returns the block count
 int gemm_trace_fetch(unsigned long long* host_out, int max_blocks);
+// the symbol of the kernel this process's last GEMM launch used (mb_debug_gemm_last_kernel) -> its length, 0 = no launch yet
+int gemm_last_kernel(char* out, int cap);
 
 // tile: 0 = auto, 64 or 128.  splits: split-K factor (only EPI_ACCUM_F32).
 int gemm_launch(int dtype, int layout, int mode, const GemmArgs& a, int splits, int tile, hipStream_t st);

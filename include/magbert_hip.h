@@ -60,6 +60,34 @@ int mb_debug_gemm_trace(unsigned long long* host_out, int max_blocks);
  * 4 key sweep done, 5 exit */
 int mb_debug_attention_trace(unsigned long long* host_out, int max_blocks);
 
+/* TEST HOOKS (tests/test_gemm_edges_gpu.py; no engine code calls them, no product path changes): they only fill the launchers'
+ * argument structures with what mb_gemm / mb_gemm_grouped_wgrad cannot set and call the same launchers the engines call.
+ *
+ * mb_debug_gemm_ex = mb_gemm plus
+ *   bseg, bseg_stride  segmented B: B's contiguous dimension is cut into pieces of bseg elements, bseg_stride elements apart (0 = off)
+ *   cvalid, overwrite  epilogue 5: store only columns [0, cvalid) dword-wise (0 = all) ; Cf = acc instead of Cf += acc
+ *   colsum_shadow      epilogue 4, may be NULL: [N] 64-bit deterministic-mode accumulator parallel to Cf; the column sums go there as
+ *                      2^44-scaled integers, and with fold != 0 the engines' fold adds them into Cf and clears the shadow
+ *   rp .. zero_grad    an AdamW rider inside the launch (blocks = 0: none): blocks workgroups update 4 * n4 weight-decayed parameters
+ *                      (shadow: bf16 copy of the whole range or NULL); lr .. grad_scale as mb_adamw_step, turned into the step's scalars
+ *                      by the same host code and written to adam_dev (device memory, 28 bytes) for the rider to read.  layout 1, tile 0.
+ *   ride_tiles         may be NULL: the padded tile count of the rider-carrying launch (0 = that launch carries none: MB_ERR_MODE)
+ * mb_debug_gemm_grouped_ex = mb_gemm_grouped_wgrad (count <= 8) plus per-problem cvalid / overwrite (arrays or NULL), the ring depth of the
+ *   64 x 64 group (stages 0 | 4 | 5) and a rider as above (128 x 128 and ping-pong tiles only).
+ * mb_debug_gemm_last_kernel: the (mangled) symbol of the kernel this process's last GEMM launch used -> its length, 0 = none yet. */
+int mb_debug_gemm_ex(int dtype, int layout, int epilogue, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                     void* C, int ldc, void* C2, float* Cf, const float* bias, const void* R, int ldr, float alpha,
+                     const mb_dropkey* drop, int splits, int tile, int bseg, size_t bseg_stride, int cvalid, int overwrite,
+                     long long* colsum_shadow, int fold, float* rp, float* rg, float* rm, float* rv, void* rshadow, size_t n4, int blocks,
+                     int zero_grad, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int correct_bias,
+                     float grad_scale, void* adam_dev, int* ride_tiles, void* stream);
+int mb_debug_gemm_grouped_ex(int dtype, int count, const int* M, const int* N, int K, const void* const* dY, const int* ldy,
+                             const void* const* X, const int* ldx, float* const* dW, const int* ldw, const int* cvalid,
+                             const int* overwrite, int tile, int stages, float* rp, float* rg, float* rm, float* rv, void* rshadow,
+                             size_t n4, int blocks, int zero_grad, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int step, int correct_bias, float grad_scale, void* adam_dev, void* stream);
+int mb_debug_gemm_last_kernel(char* out, int cap);
+
 /* `count` (<= 4) weight gradients dW_g[M_g][N_g] += dY_g[K][M_g]^T X_g[K][N_g] in ONE launch (fp32 accumulate) -- the
  * four torch.nn.Linear weight gradients autograd produces per BertLayer (mm_backward under loss.backward(),
  * multimodal_driver.py:378).  Every M_g, N_g must be a multiple of `tile` (64 | 128 | 256 = the 256 x 128 ping-pong tile, bf16: M_g % 256, N_g % 128) and K a

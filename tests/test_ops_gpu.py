@@ -69,7 +69,9 @@ def gemm(dt, tdt, layout, epi, M, N, K, A, B, bias=None, R=None, alpha=1.0, drop
 @pytest.mark.parametrize("dt,tdt", DTS)
 @pytest.mark.parametrize("M,N,K,tile", [(150, 192, 128, 64), (2400, 768, 768, 0), (300, 256, 3072, 128), (48, 768, 768, 64),
                                         (2400, 3072, 768, 0), (2400, 2304, 768, 256), (300, 136, 192, 256),   # 256 = eight-wave 256 x 128 tiles (bf16; fp32 falls back to 128)
-                                        # 12872 = eight-wave 128 x 64 tiles, 128 k per stage (bf16; what it cannot take runs 64 x 64)
+                                        # 12872 = eight-wave 128 x 64 tiles, 128 k per stage (bf16; what it cannot take runs 64 x 64 -- and of the
+                                        # four epilogues below only bias and bias_drop_res have a ping-pong form: gelu and bias_f32 run 64 x 64 here;
+                                        # tests/test_gemm_edges_gpu.py asserts which kernel ran)
                                         (2400, 768, 3072, 12872), (2400, 768, 768, 12872), (300, 200, 384, 12872), (130, 64, 512, 12872),
                                         # 25672 = eight-wave 256 x 64 tiles, 64 k per stage (the same launches at T = 4096)
                                         (4096, 768, 3072, 25672), (4096, 768, 768, 0), (600, 200, 192, 25672), (260, 64, 320, 25672)])
@@ -90,12 +92,13 @@ def test_gemm_nt_epilogues(dt, tdt, M, N, K, tile):
     c, _, _ = gemm(dt, tdt, _lib.GEMM_NT, _lib.EPI_BIAS_DROP_RES, M, N, K, A, B, bias=bias, R=R, drop=key, tile=tile)
     close(c, ((ref + bias.double()) * mask.double() + R.double()).float(), dt, "bias_drop_res")
     _, _, cf = gemm(dt, tdt, _lib.GEMM_NT, _lib.EPI_BIAS_F32, M, N, K, A, B, bias=bias, tile=tile)
-    close(cf, (ref + bias.double()).float(), _lib.DT_F32 if dt == _lib.DT_F32 else dt, "bias_f32")
+    close(cf, (ref + bias.double()).float(), _lib.DT_F32, "bias_f32")       # an fp32 output, never rounded to bf16: the fp32 bound in both modes
 
 
 @pytest.mark.parametrize("dt,tdt", DTS)
 @pytest.mark.parametrize("M,N,K,tile", [(150, 192, 128, 64), (2400, 768, 3072, 0), (2400, 3072, 768, 128), (2400, 768, 2304, 64),
                                         (100, 128, 64, 128), (2400, 768, 768, 128), (2400, 3072, 768, 0), (500, 384, 192, 256),
+                                        # (12872 / 25672: add_res runs the ping-pong forms, dgelu has none and runs 64 x 64 / 128 x 128)
                                         (2400, 768, 3072, 12872), (2400, 768, 2304, 12872), (150, 192, 384, 12872), (2400, 768, 768, 12872),
                                         (4096, 768, 3072, 0), (4096, 768, 2304, 25672), (300, 192, 192, 25672)])
 def test_gemm_nn_dgrad(dt, tdt, M, N, K, tile):
@@ -115,9 +118,11 @@ def test_gemm_nn_dgrad(dt, tdt, M, N, K, tile):
                                                # K % 64 == 0 -> LDS-DMA ring + ds_read_b64_tr_b16 path
                                                (768, 768, 2432, 3, 64), (3072, 768, 2432, 2, 128), (768, 3072, 2432, 2, 128),
                                                (1536, 64, 2432, 8, 64), (2304, 768, 2432, 1, 0), (128, 128, 64, 1, 128),
-                                               # 256 = the eight-wave ping-pong 256 x 128 tile (gemm_pp.hip; bf16): shortest k range (2 stages),
-                                               # odd / even stage counts (the three-slot ring wraps differently), partial XCD regions
-                                               (256, 128, 128, 1, 256), (768, 768, 2432, 1, 256), (768, 384, 2368, 1, 256), (3072, 768, 192, 1, 256)])
+                                               # 256 = the eight-wave ping-pong 256 x 128 tile (gemm_pp.hip; bf16): it needs three k stages, so
+                                               # K = 128 (two) runs the 128 x 128 four-wave kernel and K = 192 is its shortest k range; odd / even
+                                               # stage counts (the three-slot ring wraps differently), partial XCD regions
+                                               (256, 128, 128, 1, 256), (256, 128, 192, 1, 256), (768, 768, 2432, 1, 256), (768, 384, 2368, 1, 256),
+                                               (3072, 768, 192, 1, 256)])
 def test_gemm_tn_wgrad(dt, tdt, M, N, K, splits, tile):
     A, B = rnd((K, M), 8, tdt), rnd((K, N), 9, tdt, 0.1)     # both [K][rows]
     init = rnd((M, N), 10, torch.float32)
