@@ -10,6 +10,21 @@ LIB_PATH = os.path.join(os.environ.get("MB_LIB_DIR") or os.path.join(_HERE, "lib
 DT_F32, DT_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_ADD_RES, EPI_DGELU, EPI_ACCUM_F32, EPI_BIAS_F32 = range(7)
+# epilogue 1 with another activation in the place of erf-GELU (layout 0 only): C = act'(u), C2 = act(u)
+EPI_BIAS_RELU, EPI_BIAS_SWISH, EPI_BIAS_GELU_NEW, EPI_BIAS_MISH = 7, 8, 9, 10
+# feed-forward activation of an engine config (hidden_act / ff_activation), by transformers' ACT2FN names; silu is swish
+ACT_GELU, ACT_RELU, ACT_SWISH, ACT_GELU_NEW, ACT_MISH = range(5)
+ACTIVATIONS = {"gelu": ACT_GELU, "relu": ACT_RELU, "swish": ACT_SWISH, "silu": ACT_SWISH, "gelu_new": ACT_GELU_NEW, "mish": ACT_MISH}
+ACT_EPILOGUE = {ACT_GELU: EPI_BIAS_GELU, ACT_RELU: EPI_BIAS_RELU, ACT_SWISH: EPI_BIAS_SWISH, ACT_GELU_NEW: EPI_BIAS_GELU_NEW,
+                ACT_MISH: EPI_BIAS_MISH}
+
+
+def activation_code(name, field):
+    """ACT_* of a config's activation name; anything else (a callable included) is not built"""
+    if isinstance(name, str) and name in ACTIVATIONS:
+        return ACTIVATIONS[name]
+    raise NotImplementedError("%s=%r: the feed-forward activations built are %s (and silu = swish)"
+                              % (field, name, ", ".join(n for n in ACTIVATIONS if n != "silu")))
 
 
 class DropKey(C.Structure):
@@ -22,7 +37,7 @@ class BertEngineConfig(C.Structure):
                 ("num_labels", C.c_int), ("visual_dim", C.c_int), ("acoustic_dim", C.c_int), ("pad_token_id", C.c_int),
                 ("layer_norm_eps", C.c_float), ("mag_layer_norm_eps", C.c_float), ("beta_shift", C.c_float),
                 ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("mag_dropout", C.c_float),
-                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int)]
+                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int), ("hidden_act", C.c_int)]
 
 
 class XlnetEngineConfig(C.Structure):
@@ -30,7 +45,7 @@ class XlnetEngineConfig(C.Structure):
                 ("num_labels", C.c_int), ("visual_dim", C.c_int), ("acoustic_dim", C.c_int), ("injection_index", C.c_int),
                 ("layer_norm_eps", C.c_float), ("mag_layer_norm_eps", C.c_float), ("beta_shift", C.c_float),
                 ("dropout", C.c_float), ("summary_last_dropout", C.c_float), ("mag_dropout", C.c_float),
-                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int)]
+                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int), ("ff_activation", C.c_int)]
 
 
 _vp, _i, _f, _sz, _u64, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64, C.c_uint32

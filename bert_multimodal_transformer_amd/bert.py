@@ -79,8 +79,7 @@ class BertConfig(object):
                  intermediate_size=3072, hidden_act="gelu", hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1,
                  max_position_embeddings=512, type_vocab_size=2, initializer_range=0.02, layer_norm_eps=1e-12,
                  pad_token_id=0, num_labels=1, **kwargs):
-        if hidden_act != "gelu":
-            raise NotImplementedError("only erf-GELU (hidden_act = \"gelu\", what the published BERT checkpoints use) is built")
+        _lib.activation_code(hidden_act, "hidden_act")       # gelu | relu | swish (silu) | gelu_new | mish; anything else raises
         self.vocab_size = vocab_size
         self.hidden_size = hidden_size
         self.num_hidden_layers = num_hidden_layers
@@ -241,12 +240,12 @@ class _Core(object):
             return _lib.XlnetEngineConfig(
                 c.vocab_size, c.d_model, c.n_layer, c.n_head, c.d_inner, c.num_labels, self.V, self.A, int(self.injection_index),
                 c.layer_norm_eps, 1e-5, float(mc.beta_shift), c.dropout, c.summary_last_dropout, float(mc.dropout_prob),
-                self.dt, int(B), int(L))
+                self.dt, int(B), int(L), _lib.activation_code(c.ff_activation, "ff_activation"))
         return _lib.BertEngineConfig(
             c.vocab_size, c.hidden_size, c.num_hidden_layers, c.num_attention_heads, c.intermediate_size,
             c.max_position_embeddings, c.type_vocab_size, c.num_labels, self.V, self.A, c.pad_token_id,
             c.layer_norm_eps, 1e-5, float(mc.beta_shift), c.hidden_dropout_prob, c.attention_probs_dropout_prob,
-            float(mc.dropout_prob), self.dt, int(B), int(L))
+            float(mc.dropout_prob), self.dt, int(B), int(L), _lib.activation_code(c.hidden_act, "hidden_act"))
 
     def _make_engine(self, B, L):
         h = C.c_void_p()

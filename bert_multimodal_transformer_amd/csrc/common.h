@@ -207,4 +207,54 @@ __device__ __forceinline__ void gelu_pair(f32x2 x, f32x2& g, f32x2& dg) {
     dg = x * 0.39894228040143268f * e + Phi;
 }
 
+// The other feed-forward activations of transformers 3.0.2 ACT2FN (config.hidden_act / config.ff_activation), each with its derivative
+// and in the form of gelu_pair: packed fp32, v_exp_f32 / v_rcp_f32 as the only transcendentals, no division, no branch.  Every
+// logistic is 1 / (1 + e^-x) with the exponent clamped at 2^120: the rcp of a finite number, so both tails end on their limits
+// (0 and 1) and 1 - sigma = e^-x sigma is a product of finite numbers -- no inf - inf or 0 * inf up to |x| = 1e4 and beyond.
+enum { ACT_GELU = 0, ACT_RELU = 1, ACT_SWISH = 2, ACT_GELU_NEW = 3, ACT_MISH = 4 };
+__device__ __forceinline__ void relu_pair(f32x2 x, f32x2& g, f32x2& dg) {
+    g = f32x2{fmaxf(x.x, 0.f), fmaxf(x.y, 0.f)};
+    dg = f32x2{x.x > 0.f ? 1.f : 0.f, x.y > 0.f ? 1.f : 0.f};    // torch's subgradient: 0 at +-0
+}
+// sigma(z) and 1 - sigma(z)
+__device__ __forceinline__ void logistic_pair(f32x2 z, f32x2& s, f32x2& s1) {
+    const f32x2 q = z * -1.44269504089f;                        // -z log2(e)
+    const f32x2 e = {__builtin_amdgcn_exp2f(fminf(q.x, 120.f)), __builtin_amdgcn_exp2f(fminf(q.y, 120.f))};
+    const f32x2 d = e + 1.0f;
+    s = f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+    s1 = e * s;
+}
+// swish / silu: x sigma(x) ; sigma (1 + x (1 - sigma))
+__device__ __forceinline__ void swish_pair(f32x2 x, f32x2& g, f32x2& dg) {
+    f32x2 s, s1;
+    logistic_pair(x, s, s1);
+    g = x * s;
+    dg = (x * s1 + 1.0f) * s;
+}
+// gelu_new: 0.5 x (1 + tanh z), z = sqrt(2 / pi) (x + 0.044715 x^3).  0.5 (1 + tanh z) = sigma(2 z) and 1 - tanh^2 z = 4 sigma (1 - sigma):
+// gelu_new = x sigma ; gelu_new' = sigma + x * 2 sigma (1 - sigma) * sqrt(2 / pi) (1 + 0.134145 x^2)
+__device__ __forceinline__ void gelu_new_pair(f32x2 x, f32x2& g, f32x2& dg) {
+    const f32x2 x2 = x * x;
+    const f32x2 z2 = (x2 * 0.0713548162726f + 1.59576912161f) * x;       // 2 z
+    f32x2 s, s1;
+    logistic_pair(z2, s, s1);
+    const f32x2 dz2 = x2 * 0.214064448818f + 1.59576912161f;             // d(2 z) / dx
+    g = x * s;
+    dg = (x * dz2) * (s * s1) + s;
+}
+// mish: x tanh(softplus x).  With w = e^x and n = w (w + 2): tanh(softplus x) = n / (n + 2), its derivative 4 w (w + 1) / (n + 2)^2.
+// x is clamped at 20 in front of the exponential: beyond it the ratio is 1 and the derivative term below 1e-16 x in fp32 anyway.
+__device__ __forceinline__ void mish_pair(f32x2 x, f32x2& g, f32x2& dg) {
+    const f32x2 q = x * 1.44269504089f;
+    const f32x2 w = {__builtin_amdgcn_exp2f(fminf(q.x, 28.8539008178f)), __builtin_amdgcn_exp2f(fminf(q.y, 28.8539008178f))};
+    const f32x2 n = (w + 2.0f) * w;
+    const f32x2 d = n + 2.0f;
+    const f32x2 r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+    const f32x2 tl = n * r, tu = r * -2.0f + 1.0f;               // n / (n + 2) below zero (no cancellation there), 1 - 2 / (n + 2) above it:
+    const f32x2 th = {x.x > 0.f ? tu.x : tl.x, x.y > 0.f ? tu.y : tl.y};      // exactly 1 once n + 2 passes 2^25, so that mish(x) = x
+    const f32x2 dth = (w * w + w) * 4.0f * r * r;
+    g = x * th;
+    dg = x * dth + th;
+}
+
 }  // namespace mb

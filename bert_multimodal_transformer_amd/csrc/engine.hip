@@ -281,6 +281,15 @@ void mb_make_dropkey(uint64_t seed, uint64_t step, uint32_t site, float p, mb_dr
     out->k0 = k.k0; out->k1 = k.k1; out->thresh = k.thresh; out->scale = k.scale;
 }
 
+// epilogue codes 7 .. 10 of the C ABI (relu, swish, gelu_new, mish; layout 0 only) -> the one internal mode and GemmArgs::act
+static int abi_epilogue(int& epilogue, int layout, GemmArgs& a) {
+    if (epilogue < MB_EPI_RELU || epilogue > MB_EPI_MISH) return MB_OK;
+    if (layout != GEMM_NT) return MB_ERR_MODE;
+    a.act = ACT_RELU + (epilogue - MB_EPI_RELU);
+    epilogue = EPI_BIAS_ACT;
+    return MB_OK;
+}
+
 int mb_gemm(int dtype, int layout, int epilogue, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
             void* C, int ldc, void* C2, float* Cf, const float* bias, const void* R, int ldr, float alpha,
             const mb_dropkey* drop, int splits, int tile, void* stream) {
@@ -288,6 +297,7 @@ int mb_gemm(int dtype, int layout, int epilogue, int M, int N, int K, const void
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.C = C; a.ldc = ldc; a.C2 = C2; a.Cf = Cf;
     a.bias = bias; a.R = R; a.ldr = ldr; a.alpha = alpha; a.drop = dk(drop); a.kchunk = K; a.colsum = nullptr;
     if (epilogue == EPI_DGELU) { a.colsum = Cf; a.Cf = nullptr; }       // epilogue 4: the fp32 pointer is the fused bias gradient
+    if (int e = abi_epilogue(epilogue, layout, a)) return e;
     return gemm_launch(dtype, layout, epilogue, a, splits, tile, (hipStream_t)stream);
 }
 
@@ -302,6 +312,7 @@ int mb_debug_gemm_ex(int dtype, int layout, int epilogue, int M, int N, int K, c
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.C = C; a.ldc = ldc; a.C2 = C2; a.Cf = Cf;
     a.bias = bias; a.R = R; a.ldr = ldr; a.alpha = alpha; a.drop = dk(drop); a.kchunk = K; a.colsum = nullptr;
     if (epilogue == EPI_DGELU) { a.colsum = Cf; a.Cf = nullptr; }
+    if (int e = abi_epilogue(epilogue, layout, a)) return e;
     a.bseg = bseg; a.bseg_stride = bseg_stride; a.cvalid = cvalid; a.overwrite = overwrite;
     if (colsum_shadow) {
         if (!a.colsum) return MB_ERR_ARG;
@@ -497,6 +508,7 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (cfg->intermediate_size % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1) return MB_ERR_SHAPE;
     if (cfg->max_seq > cfg->max_position || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
+    if (cfg->hidden_act < ACT_GELU || cfg->hidden_act > ACT_MISH) return MB_ERR_ARG;
     mb_bert_engine* e = new mb_bert_engine();
     e->c = *cfg;
     e->read_env();
@@ -621,8 +633,8 @@ static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const
         const Prefetch pf2 = {(e->prefetch && l + 1 < c.num_layers && (l + 1 < l1 || last)) ? e->W(e->lo[l + 1].wqkv) : nullptr, (size_t)4 * H * H * wes, nullptr};
         CK(ln_forward(dt, ws + w.s1, P + o.ln1w, P + o.ln1b, c.layer_norm_eps, ws + w.y1, (float*)(ws + w.st1),
                       (float*)(ws + w.st1) + T, T, H, kNoDrop, st, pf1));
-        CK(gemm(dt, GEMM_NT, EPI_BIAS_GELU, T, I, H, ws + w.y1, H, e->W(o.w1), H, ws + w.u, I, ws + w.g, nullptr, P + o.b1,
-                nullptr, 0, kNoDrop, 1, 0, st));
+        CK(gemm(dt, GEMM_NT, ffn_act_mode(c.hidden_act), T, I, H, ws + w.y1, H, e->W(o.w1), H, ws + w.u, I, ws + w.g, nullptr, P + o.b1,
+                nullptr, 0, kNoDrop, 1, 0, st, 0, 0, GradAcc{}, c.hidden_act));
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, T, H, I, ws + w.g, I, e->W(o.w2), I, ws + w.s2, H, nullptr, nullptr,
                 P + o.b2, ws + w.y1, H, e->key(SITE_LAYER0 + 4 * l + 2, c.hidden_dropout), 1, 0, st));
         CK(ln_forward(dt, ws + w.s2, P + o.ln2w, P + o.ln2b, c.layer_norm_eps, ws + e->ws_x[l + 1], (float*)(ws + w.st2),

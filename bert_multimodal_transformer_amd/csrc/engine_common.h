@@ -106,13 +106,17 @@ struct MagWs {
     }
 };
 
+// the FFN1 forward launch of a configured activation (mb_*_config: 0 = gelu ... 4 = mish): erf-GELU keeps its own epilogue mode
+inline int ffn_act_mode(int act) { return act == ACT_GELU ? EPI_BIAS_GELU : EPI_BIAS_ACT; }
+
 #define CK(x) do { int _e = (x); if (_e) { mb::ck_trace(#x, __FILE__, __LINE__, _e); return _e; } } while (0)
 
 inline int gemm(int dtype, int layout, int mode, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
          int ldc, void* C2, float* Cf, const float* bias, const void* R, int ldr, DropKey drop, int splits, int tile,
-         hipStream_t st, int bseg = 0, size_t bseg_stride = 0, GradAcc acc = {}) {
+         hipStream_t st, int bseg = 0, size_t bseg_stride = 0, GradAcc acc = {}, int act = 0) {
     GemmArgs a = {};
     a.acc = acc;
+    a.act = act;                                       // EPI_BIAS_ACT only
     a.bseg = bseg; a.bseg_stride = bseg_stride;        // segmented B (kernels.h): pieces of B's contiguous dimension in separate tensors
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb;
     a.C = C; a.ldc = ldc; a.C2 = C2; a.Cf = Cf; a.bias = bias; a.R = R; a.ldr = ldr; a.alpha = 1.0f; a.drop = drop;

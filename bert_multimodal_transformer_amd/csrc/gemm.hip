@@ -912,6 +912,9 @@ static int launch_T(const GemmArgs& a, int layout, int mode, int splits, int til
             case EPI_BIAS: return launch_tile<T, false, false, EPI_BIAS>(a, splits, tile, st);
             case EPI_BIAS_F32: return launch_tile<T, false, false, EPI_BIAS_F32>(a, splits, tile, st);
             case EPI_BIAS_GELU: return launch_tile<T, false, false, EPI_BIAS_GELU>(a, splits, tile, st);
+            case EPI_BIAS_ACT:
+                if (a.act < ACT_RELU || a.act > ACT_MISH) return MB_ERR_MODE;
+                return launch_tile<T, false, false, EPI_BIAS_ACT>(a, splits, tile, st);
             case EPI_BIAS_DROP_RES: return launch_tile<T, false, false, EPI_BIAS_DROP_RES>(a, splits, tile, st);
             case EPI_ADD_RES: return launch_tile<T, false, false, EPI_ADD_RES>(a, splits, tile, st);
             default: return MB_ERR_MODE;

@@ -386,6 +386,7 @@ int gemm_pp_launch(bool ak, bool bk, int mode, const GemmArgs& p, dim3 grid, hip
     }
     MB_PP(false, false, EPI_BIAS)
     MB_PP(false, false, EPI_BIAS_GELU)
+    MB_PP(false, false, EPI_BIAS_ACT)
     MB_PP(false, true, EPI_DGELU)
     MB_PP(true, true, EPI_ACCUM_F32)
 #undef MB_PP

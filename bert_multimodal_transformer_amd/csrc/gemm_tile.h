@@ -108,17 +108,19 @@ struct EpiPre {
     bf16x8 r[HAS_R ? NR : 1];
     float bias8[8];
     DropKey key;
+    int act;                            // EPI_BIAS_ACT: GemmArgs::act, pinned like the three below
     int ldc, cvalid, overwrite;         // scalars of the row pass, read from the kernel arguments HERE (pinned): left to the compiler, one of
                                         // them ended up as an s_load inside the k loop, whose waits count scalar loads (tests/test_host_cpu.py)
     __device__ __forceinline__ void fetch(const GemmArgs& p, int m0, int n0, int tid) {
         ldc = p.ldc; cvalid = p.cvalid; overwrite = p.overwrite;
         asm volatile("" : "+s"(ldc), "+s"(cvalid), "+s"(overwrite));
+        if constexpr (MODE == EPI_BIAS_ACT) { act = p.act; asm volatile("" : "+s"(act)); }
         key = p.drop;
         key.resolve();
         const int n = n0 + (tid % TPR) * 8;
 #pragma unroll
         for (int q = 0; q < 8; ++q) bias8[q] = 0.f;
-        if constexpr (MODE == EPI_BIAS || MODE == EPI_BIAS_F32 || MODE == EPI_BIAS_GELU || MODE == EPI_BIAS_DROP_RES) {
+        if constexpr (MODE == EPI_BIAS || MODE == EPI_BIAS_F32 || MODE == EPI_BIAS_GELU || MODE == EPI_BIAS_DROP_RES || MODE == EPI_BIAS_ACT) {
             if (p.bias && n < p.N) Vec8<float>::load(p.bias + n, bias8);
         }
         if constexpr (HAS_R) {
@@ -207,7 +209,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[KS
 #pragma unroll
             for (int q = 0; q < 4; ++q) { v[q] = a[q]; v[4 + q] = b[q]; }
         }
-        // the residual / gelu' row: prefetched (bf16) or read here (fp32)
+        // the residual / saved-derivative row: prefetched (bf16) or read here (fp32)
         float res[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if constexpr (MODE == EPI_BIAS_DROP_RES || MODE == EPI_ADD_RES || MODE == EPI_DGELU) {
             if constexpr (Pre::HAS_R) {
@@ -244,6 +246,32 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[KS
             }
             Vec8<T>::store(C + off, v);
             Vec8<T>::store((T*)p.C2 + off, g);
+        } else if constexpr (MODE == EPI_BIAS_ACT) {
+            // mode 1 with another activation: the same u, the same two planes (C = act'(u) of the unrounded u, C2 = act(u) [* dropout]),
+            // the pair function chosen per row by a switch on a scalar register
+            float g[8];
+            const uint32_t gidx = (uint32_t)m * (uint32_t)p.N + (uint32_t)n;
+#define MB_ACT_ROW(FN) \
+            _Pragma("unroll") for (int q = 0; q < 8; q += 2) { \
+                const f32x2 u = {v[q] + bias8[q], v[q + 1] + bias8[q + 1]}; \
+                f32x2 gg, dg; \
+                FN(u, gg, dg); \
+                g[q] = gg.x; g[q + 1] = gg.y; \
+                v[q] = dg.x; v[q + 1] = dg.y; \
+            }
+            switch (pre.act) {
+                case ACT_RELU: MB_ACT_ROW(relu_pair) break;
+                case ACT_SWISH: MB_ACT_ROW(swish_pair) break;
+                case ACT_GELU_NEW: MB_ACT_ROW(gelu_new_pair) break;
+                default: MB_ACT_ROW(mish_pair) break;             // ACT_MISH (the launcher admits no other value)
+            }
+#undef MB_ACT_ROW
+            if (dkey.thresh != 0u) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) g[q] *= drop_mult(dkey, gidx + q);
+            }
+            Vec8<T>::store(C + off, v);
+            Vec8<T>::store((T*)p.C2 + off, g);
         } else if constexpr (MODE == EPI_BIAS_DROP_RES) {
             const uint32_t idx = (uint32_t)m * (uint32_t)p.N + (uint32_t)n;
 #pragma unroll
@@ -256,7 +284,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[KS
         } else if constexpr (MODE == EPI_DGELU) {
             const uint32_t gidx = (uint32_t)m * (uint32_t)p.N + (uint32_t)n;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { v[q] *= res[q] * drop_mult(dkey, gidx + q); cs[q] += v[q]; }      // R = gelu'(u) saved by EPI_BIAS_GELU
+            for (int q = 0; q < 8; ++q) { v[q] *= res[q] * drop_mult(dkey, gidx + q); cs[q] += v[q]; }      // R = the derivative saved by mode 1 / 7
             Vec8<T>::store(C + off, v);
         } else if constexpr (MODE == EPI_ACCUM_F32) {
             float* dst = p.Cf + off;

@@ -32,9 +32,10 @@ enum { EPI_BIAS = 0,          // C = alpha*acc + bias                           
        EPI_BIAS_GELU = 1,     // u = acc + bias ; C = gelu'(u) ; C2 = gelu(u) [* dropout]  (T out x2)
        EPI_BIAS_DROP_RES = 2, // C = dropout(acc + bias) + R                            (T out)
        EPI_ADD_RES = 3,       // C = acc (+ R)                                          (T out)
-       EPI_DGELU = 4,         // C = acc * R [* dropout], R = gelu'(u) saved by mode 1  (T out)
+       EPI_DGELU = 4,         // C = acc * R [* dropout], R = the derivative saved by mode 1 / 7  (T out)
        EPI_ACCUM_F32 = 5,     // Cf += acc   (atomic when split-K)                      (fp32 out)
-       EPI_BIAS_F32 = 6 };    // Cf = alpha*acc + bias                                  (fp32 out)
+       EPI_BIAS_F32 = 6,      // Cf = alpha*acc + bias                                  (fp32 out)
+       EPI_BIAS_ACT = 7 };    // mode 1 with GemmArgs::act (common.h ACT_RELU ... ACT_MISH) in the place of erf-GELU  (T out x2)
 
 struct AdamArgs {
     float lr, beta1, beta2, eps, weight_decay, step_size;   // step_size = lr*sqrt(1-b2^t)/(1-b1^t)
@@ -44,8 +45,9 @@ struct AdamArgs {
 struct GemmArgs {
     const void* A; const void* B;
     int M, N, K, lda, ldb;
-    void* C; int ldc;          // T output (modes 0-4)
-    void* C2;                  // second T output (mode 1), same ldc
+    void* C; int ldc;          // T output (modes 0-4, 7)
+    int act;                   // mode 7: the activation, ACT_RELU | ACT_SWISH | ACT_GELU_NEW | ACT_MISH (wave-uniform switch in the epilogue)
+    void* C2;                  // second T output (modes 1, 7), same ldc
     float* Cf;                 // fp32 output (modes 5, 6), ldc
     const float* bias;         // [N] fp32 or null
     float* colsum;             // EPI_DGELU: if non-null, colsum[n] += sum_m C[m][n] (bias grad of the previous Linear)

@@ -238,6 +238,7 @@ int mb_xlnet_create(const mb_xlnet_config* cfg, mb_xlnet_engine** out) {
     if (cfg->d_inner % 128 || cfg->max_seq < 1 || cfg->max_seq > 512 || cfg->max_batch < 1 || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->injection_index < 0 || cfg->injection_index >= cfg->n_layer) return MB_ERR_ARG;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
+    if (cfg->ff_activation < ACT_GELU || cfg->ff_activation > ACT_MISH) return MB_ERR_ARG;
     mb_xlnet_engine* e = new mb_xlnet_engine();
     e->c = *cfg;
     e->read_env();
@@ -374,8 +375,8 @@ static int xl_forward_range(mb_xlnet_engine* e, const int64_t* input_ids, const 
         CK(ln_forward(dt, ws + w.s1, P + o.ralnw, P + o.ralnb, c.layer_norm_eps, ws + w.y1, (float*)(ws + w.st1),
                       (float*)(ws + w.st1) + T, T, H, kNoDrop, st, pf1));
         // feed forward: layer_1 -> gelu -> dropout -> layer_2 -> dropout -> LayerNorm(. + inp)
-        CK(gemm(dt, GEMM_NT, EPI_BIAS_GELU, T, I, H, ws + w.y1, H, e->W(o.w1), H, ws + w.u, I, ws + w.g, nullptr, P + o.b1, nullptr, 0,
-                e->key(XS_LAYER0 + 8 * l + 2, pd), 1, 0, st));
+        CK(gemm(dt, GEMM_NT, ffn_act_mode(c.ff_activation), T, I, H, ws + w.y1, H, e->W(o.w1), H, ws + w.u, I, ws + w.g, nullptr, P + o.b1, nullptr, 0,
+                e->key(XS_LAYER0 + 8 * l + 2, pd), 1, 0, st, 0, 0, GradAcc{}, c.ff_activation));
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, T, H, I, ws + w.g, I, e->W(o.w2), I, ws + w.s2, H, nullptr, nullptr, P + o.b2,
                 ws + w.y1, H, e->key(XS_LAYER0 + 8 * l + 3, pd), 1, 0, st));
         CK(ln_forward(dt, ws + w.s2, P + o.fflnw, P + o.fflnb, c.layer_norm_eps, ws + e->ws_x[l + 1], (float*)(ws + w.st2),
@@ -862,7 +863,8 @@ int mb_xlnet_query_stream(mb_xlnet_engine* e, const float* target_mapping, int M
         // post_attention and the feed-forward block, the content stream's weights on M rows per sample
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, R, H, H, sc + q.vecg, H, e->W(o.o), H, sc + q.s1, H, nullptr, nullptr, nullptr, g, H, kNoDrop, 1, 0, st));
         CK(ln_forward(dt, sc + q.s1, P + o.ralnw, P + o.ralnb, c.layer_norm_eps, sc + q.y1, mean, rstd, R, H, kNoDrop, st));
-        CK(gemm(dt, GEMM_NT, EPI_BIAS_GELU, R, I, H, sc + q.y1, H, e->W(o.w1), H, sc + q.u, I, sc + q.gl, nullptr, P + o.b1, nullptr, 0, kNoDrop, 1, 0, st));
+        CK(gemm(dt, GEMM_NT, ffn_act_mode(c.ff_activation), R, I, H, sc + q.y1, H, e->W(o.w1), H, sc + q.u, I, sc + q.gl, nullptr, P + o.b1, nullptr, 0, kNoDrop, 1, 0, st,
+                0, 0, GradAcc{}, c.ff_activation));
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, R, H, I, sc + q.gl, I, e->W(o.w2), I, sc + q.s2, H, nullptr, nullptr, P + o.b2, sc + q.y1, H, kNoDrop, 1, 0, st));
         CK(ln_forward(dt, sc + q.s2, P + o.fflnw, P + o.fflnb, c.layer_norm_eps, state(l + 1), mean, rstd, R, H, kNoDrop, st));
     }

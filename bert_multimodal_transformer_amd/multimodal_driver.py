@@ -128,7 +128,22 @@ def get_parser():
     parser.add_argument("--freeze_embeddings", type=str2bool, nargs="?", const=True, default=False,
                         help="freeze the embedding tables (MAG-BERT: word, position, token-type and their LayerNorm; MAG-XLNet: the "
                              "word table): no embedding backward, no update of the tables")
+    parser.add_argument("--hidden_act", type=str, default=None, choices=sorted(_lib_activations()),
+                        help="feed-forward activation of either model (BertConfig.hidden_act / XLNetConfig.ff_activation); default: "
+                             "what the configuration says (gelu unless a checkpoint's config.json names another)")
     return parser
+
+
+def _lib_activations():
+    from ._lib import ACTIVATIONS
+    return ACTIVATIONS
+
+
+def with_hidden_act(config, name):
+    """--hidden_act: the configuration with its feed-forward activation replaced (None = as it is)"""
+    if name is not None:
+        setattr(config, "ff_activation" if hasattr(config, "ff_activation") else "hidden_act", name)
+    return config
 
 
 def parse_args(argv=None):
@@ -409,9 +424,9 @@ def prep_for_training(num_train_optimization_steps: int):
             model = MAG_BertForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
                 compute_dtype=dt, max_seq_length=args.max_seq_length,
-                config=read_config_beside(args.pretrained, 1) or bert_config(args.model))
+                config=with_hidden_act(read_config_beside(args.pretrained, 1) or bert_config(args.model), args.hidden_act))
         else:       # offline: fresh init by the reference's init law
-            model = MAG_BertForSequenceClassification(bert_config(args.model), multimodal_config, visual_dim=V,
+            model = MAG_BertForSequenceClassification(with_hidden_act(bert_config(args.model), args.hidden_act), multimodal_config, visual_dim=V,
                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     elif args.model in XLNET_MODELS:
         from .xlnet import MAG_XLNetForSequenceClassification, read_xlnet_config_beside
@@ -420,9 +435,9 @@ def prep_for_training(num_train_optimization_steps: int):
             model = MAG_XLNetForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
                 compute_dtype=dt, max_seq_length=args.max_seq_length,
-                config=read_xlnet_config_beside(args.pretrained, 1) or xlnet_config(args.model))
+                config=with_hidden_act(read_xlnet_config_beside(args.pretrained, 1) or xlnet_config(args.model), args.hidden_act))
         else:
-            model = MAG_XLNetForSequenceClassification(xlnet_config(args.model), multimodal_config, visual_dim=V,
+            model = MAG_XLNetForSequenceClassification(with_hidden_act(xlnet_config(args.model), args.hidden_act), multimodal_config, visual_dim=V,
                                                        acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
     model.to(_device())
     if args.freeze_layers > 0 or args.freeze_embeddings:

@@ -77,10 +77,12 @@ class XLNetConfig(object):
                  attn_type="bi", initializer_range=0.02, layer_norm_eps=1e-12, dropout=0.1, mem_len=None, reuse_len=None,
                  bi_data=False, clamp_len=-1, same_length=False, summary_type="last", summary_use_proj=True,
                  summary_activation="tanh", summary_last_dropout=0.1, num_labels=1, **kwargs):
-        if ff_activation != "gelu" or attn_type != "bi" or bi_data or clamp_len != -1 or reuse_len not in (None, 0) \
+        _lib.activation_code(ff_activation, "ff_activation")      # gelu | relu | swish (silu) | gelu_new | mish; anything else raises
+        if attn_type != "bi" or bi_data or clamp_len != -1 or reuse_len not in (None, 0) \
                 or summary_type != "last" or not summary_use_proj or summary_activation != "tanh":
             raise NotImplementedError("only the configuration of the published XLNet checkpoints that multimodal_driver.py uses is built "
-                                      "(gelu, attn_type bi, summary: last + tanh projection)")
+                                      "(attn_type bi, summary: last + tanh projection)")
+        self.ff_activation = ff_activation
         self.mem_len = mem_len          # > 0 with use_cache: forward() also returns new_mems (xlnet.py:81-91, 363-365, 406-407)
         self.vocab_size = vocab_size
         self.d_model = d_model

@@ -42,11 +42,17 @@ void mb_make_dropkey(uint64_t seed, uint64_t step, uint32_t site, float p, mb_dr
  * layout 2 (TN): A[K][M], B[K][N]          wgrad    dW += dY^T X   (fp32 accumulate, split-K)
  * epilogue: 0 C=alpha*acc+bias | 1 u=acc+bias: C=gelu'(u), C2=gelu(u) | 2 C=dropout(acc+bias)+R | 3 C=acc+R | 4 C=acc*R (R = the gelu'(u) saved by 1)
  *           5 Cf+=acc (fp32) | 6 Cf=alpha*acc+bias (fp32)
+ *           7 relu | 8 swish (silu) | 9 gelu_new (tanh form) | 10 mish: epilogue 1 with that activation in the place of erf-GELU --
+ *           C = act'(u), C2 = act(u) [* dropout]; layout 0 only (any other layout: MB_ERR_MODE).  What epilogue 4 reads as R is the
+ *           derivative plane C of epilogue 1 or of 7 .. 10, whichever the forward ran.
  * With epilogue 4, Cf (fp32 [N], may be NULL) receives += the column sums of C: the bias gradient of the Linear in front.
  * tile: 0 = chosen by shape (what the engines pass) | 64 | 128 | 12864 (128 x 64, four waves) | 256 (256 x 128 eight-wave ping-pong, bf16)
  *       | 12872 (128 x 64 eight-wave ping-pong, bf16: the choice for N = 768 at one tile per CU) | 25672 (256 x 64, the same at T = 4096);
  *       a tile that cannot take the problem
  *       (dtype, epilogue, k range) falls back to the next smaller one.  splits > 1: split-K (layout 2 only). */
+enum { MB_EPI_RELU = 7, MB_EPI_SWISH = 8, MB_EPI_GELU_NEW = 9, MB_EPI_MISH = 10 };
+/* feed-forward activation of an engine (mb_bert_config.hidden_act, mb_xlnet_config.ff_activation): transformers' ACT2FN names */
+enum { MB_ACT_GELU = 0, MB_ACT_RELU = 1, MB_ACT_SWISH = 2, MB_ACT_GELU_NEW = 3, MB_ACT_MISH = 4 };
 int mb_gemm(int dtype, int layout, int epilogue, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
             void* C, int ldc, void* C2, float* Cf, const float* bias, const void* R, int ldr, float alpha,
             const mb_dropkey* drop, int splits, int tile, void* stream);
@@ -190,6 +196,8 @@ typedef struct {
     int dtype;       /* MB_DT_* */
     int max_batch, max_seq;      /* max_seq <= min(512, max_position); above 128 the attention runs the tiled kernels and the
                                     workspace holds their row statistics (engines of max_seq <= 128 carve exactly what they did) */
+    int hidden_act;              /* MB_ACT_*: the activation of BertIntermediate (config.hidden_act); 0 = erf-GELU, what a zero-initialised
+                                    config has always run.  Fixed at create time; any other value: MB_ERR_ARG */
 } mb_bert_config;
 
 typedef struct mb_bert_engine mb_bert_engine;
@@ -413,6 +421,8 @@ typedef struct {
     float dropout, summary_last_dropout, mag_dropout;
     int dtype;
     int max_batch, max_seq;
+    int ff_activation;           /* MB_ACT_*: the activation of XLNetFeedForward (config.ff_activation), layers and query stream; 0 = erf-GELU.
+                                    Any other value: MB_ERR_ARG */
 } mb_xlnet_config;
 
 typedef struct mb_xlnet_engine mb_xlnet_engine;
