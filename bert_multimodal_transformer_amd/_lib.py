@@ -37,7 +37,23 @@ class BertEngineConfig(C.Structure):
                 ("num_labels", C.c_int), ("visual_dim", C.c_int), ("acoustic_dim", C.c_int), ("pad_token_id", C.c_int),
                 ("layer_norm_eps", C.c_float), ("mag_layer_norm_eps", C.c_float), ("beta_shift", C.c_float),
                 ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("mag_dropout", C.c_float),
-                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int), ("hidden_act", C.c_int)]
+                ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int), ("injection_index", C.c_int),
+                ("hidden_act", C.c_int)]
+    # mb_bert_config keeps hidden_act as its last field (include/magbert_hip.h), so injection_index lies in front of it in memory;
+    # POSITIONAL arguments keep the order in which the fields were added -- hidden_act the 21st, injection_index the 22nd -- so every
+    # caller written before the field existed builds the config it always built
+    POSITIONAL = tuple(n for n, _ in _fields_ if n != "injection_index") + ("injection_index",)
+
+    def __init__(self, *args, **kw):
+        if len(args) > len(self.POSITIONAL):
+            raise TypeError("too many initializers")
+        super().__init__()
+        for name, value in zip(self.POSITIONAL, args):
+            setattr(self, name, value)
+        for name, value in kw.items():
+            if name not in self.POSITIONAL:
+                raise TypeError("BertEngineConfig has no field %r" % name)
+            setattr(self, name, value)
 
 
 class XlnetEngineConfig(C.Structure):

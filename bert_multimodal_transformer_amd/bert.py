@@ -31,9 +31,10 @@ from .global_configs import ACOUSTIC_DIM, VISUAL_DIM
 SUPPORTED_HIDDEN_SIZES = (256, 512, 768, 1024)      # what the row kernels, MAG and the head are instantiated for (heads of 64)
 
 
-def check_bert_sizes(config):
+def check_bert_sizes(config, injection_index=None):
     """The model sizes the MAG-BERT engine runs: hidden_size in SUPPORTED_HIDDEN_SIZES with heads of 64 (the compact BERTs 256 / 4 and
-    512 / 8, bert-base 768 / 12, bert-large 1024 / 16), any depth, intermediate_size a multiple of 128.  Raises ValueError otherwise."""
+    512 / 8, bert-base 768 / 12, bert-large 1024 / 16), any depth, intermediate_size a multiple of 128; MAG in front of an existing
+    layer.  Raises ValueError otherwise."""
     H, nh, I, NL = (int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size), int(config.num_hidden_layers))
     if H not in SUPPORTED_HIDDEN_SIZES:
         raise ValueError("hidden_size = %d: the HIP engine runs hidden sizes %s (heads of 64)" % (H, ", ".join(map(str, SUPPORTED_HIDDEN_SIZES))))
@@ -44,6 +45,9 @@ def check_bert_sizes(config):
         raise ValueError("intermediate_size = %d: must be a multiple of 128" % I)
     if NL < 1:
         raise ValueError("num_hidden_layers = %d: at least one layer" % NL)
+    if injection_index is not None and not 0 <= int(injection_index) < NL:
+        raise ValueError("injection_index = %d: MAG is applied in front of a layer, 0 <= injection_index < num_hidden_layers = %d"
+                         % (int(injection_index), NL))
 
 
 class BertConfig(object):
@@ -178,10 +182,12 @@ class _Core(object):
     """Flat parameter/gradient storage + engine handle shared by the model classes."""
 
     def __init__(self, config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, kind="bert",
-                 injection_index=1, max_seq_length=None):
+                 injection_index=None, max_seq_length=None):
         self.kind = kind                     # "bert" (mb_bert_*) or "xlnet" (mb_xlnet_*)
+        if injection_index is None:          # the references' positions: behind the embeddings | XLNET_INJECTION_INDEX
+            injection_index = 0 if kind == "bert" else 1
         if kind == "bert":
-            check_bert_sizes(config)         # a clear message instead of the engine's "unsupported shape"
+            check_bert_sizes(config, injection_index)         # a clear message instead of the engine's "unsupported shape" / "invalid argument"
         else:
             from .xlnet import check_xlnet_sizes
             check_xlnet_sizes(config, injection_index)
@@ -245,7 +251,8 @@ class _Core(object):
             c.vocab_size, c.hidden_size, c.num_hidden_layers, c.num_attention_heads, c.intermediate_size,
             c.max_position_embeddings, c.type_vocab_size, c.num_labels, self.V, self.A, c.pad_token_id,
             c.layer_norm_eps, 1e-5, float(mc.beta_shift), c.hidden_dropout_prob, c.attention_probs_dropout_prob,
-            float(mc.dropout_prob), self.dt, int(B), int(L), _lib.activation_code(c.hidden_act, "hidden_act"))
+            float(mc.dropout_prob), self.dt, int(B), int(L), _lib.activation_code(c.hidden_act, "hidden_act"),
+            int(self.injection_index))
 
     def _make_engine(self, B, L):
         h = C.c_void_p()
@@ -688,7 +695,9 @@ class _Core(object):
         return self.ws[off: off + B * L * H * es].view(self.compute_dtype).view(B, L, H).float()
 
     def hidden_states(self, B, L):
-        """all_hidden_states of the last forward: n_layers + 1 tensors [B, L, H] (bert.py:227-237 / xlnet.py:363-392)"""
+        """all_hidden_states of the last forward: n_layers + 1 tensors [B, L, H] (bert.py:227-237 / xlnet.py:363-392).  MAG-BERT: entry
+        i is the tensor layer i reads, so entry injection_index is MAG's output; MAG-XLNet: the tensor in front of the gate, as its
+        reference collects it."""
         return tuple(self._act(self._fn("hidden_state")(self.handle, i), B, L) for i in range(self.n_layers + 1))
 
     def xl_attentions(self, B, L, training):
@@ -1211,14 +1220,20 @@ class MAG_BertModel(_MagBertBase):
     (not differentiable; the trainable surface is MAG_BertForSequenceClassification, which is what the driver uses)."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None, _core=None, max_seq_length=None):
+                 compute_dtype=torch.float32, device=None, _core=None, max_seq_length=None, injection_index=0):
         """max_seq_length: the longest sequence this instance will run (None or <= 128: 128; at most
-        config.max_position_embeddings, ValueError above)."""
+        config.max_position_embeddings, ValueError above).
+        injection_index: MAG is applied in front of encoder layer `injection_index` (0 <= injection_index < num_hidden_layers,
+        ValueError otherwise).  0 is the reference's model, embeddings -> MAG -> layers; with j >= 1 the embeddings feed layers
+        0 .. j-1 and MAG(output of layer j-1, visual, acoustic) is what layer j reads.  A constructor argument, not part of the
+        state dict: parameters, keys and checkpoints are the same for every value.  hidden_states[i] stays "the tensor layer i
+        reads" for every value, so entry injection_index is the gate's OUTPUT (MAG-XLNet's list holds the tensor in front of the
+        gate, as its reference collects it)."""
         super().__init__()
         self.config = config
         own = _core is None
         self._core = _core or _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device,
-                                    max_seq_length=max_seq_length)
+                                    max_seq_length=max_seq_length, injection_index=injection_index)
         _attach_parameters(self, self._core, prefix_filter="bert.", strip="bert.")
         if own:
             self.init_weights()
@@ -1270,12 +1285,13 @@ class MAG_BertForSequenceClassification(_FusedStep, _MagBertBase):
     """bert.py:240-324."""
 
     def __init__(self, config, multimodal_config, visual_dim=VISUAL_DIM, acoustic_dim=ACOUSTIC_DIM,
-                 compute_dtype=torch.float32, device=None, max_seq_length=None):
-        """max_seq_length: as MAG_BertModel's."""
+                 compute_dtype=torch.float32, device=None, max_seq_length=None, injection_index=0):
+        """max_seq_length, injection_index: as MAG_BertModel's."""
         super().__init__()
         self.config = config
         self.num_labels = config.num_labels
-        self._core = _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, max_seq_length=max_seq_length)
+        self._core = _Core(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, max_seq_length=max_seq_length,
+                           injection_index=injection_index)
         self.bert = MAG_BertModel(config, multimodal_config, visual_dim, acoustic_dim, compute_dtype, device, _core=self._core)
         self.dropout = nn.Dropout(config.hidden_dropout_prob)        # bert.py:246 (p lives in the engine config)
         _attach_parameters(self, self._core, prefix_filter="classifier.")

@@ -43,7 +43,9 @@ struct mb_bert_engine : StepMixin {
     // workspace
     MagWs mw;
     size_t ws_mag, ws_emb, ws_emb_st, ws_head_z, ws_head_pooled, ws_logits;
-    std::vector<size_t> ws_x;
+    std::vector<size_t> ws_x;      // ws_x[l]: the tensor layer l reads (l = num_layers: the last output)
+    size_t ws_pre = 0;             // injection_index >= 1 only: the output of layer injection_index - 1 = what MAG's gate reads (it writes ws_x[injection_index])
+    int mag_nblk = 0;              // slabs MAG's gate backward wrote into slot num_layers of the LayerNorm partial buffers
     std::vector<LayerWs> lw;
     size_t ws_ds[2], ws_dzd[2], ws_ds2[2], ws_dzd2[2], ws_du[2], ws_dqkv[2];   // dY operands of the wgrads: ping-pong by layer parity (the workspace layout of the
                                                                                // retired side-stream scheme: every reader of a layer's set now runs inside that layer's stage)
@@ -167,6 +169,8 @@ static void build_layout(mb_bert_engine* e) {
     e->ws_emb_st = w.take(2 * T * 4);
     e->ws_x.resize(c.num_layers + 1);
     for (int l = 0; l <= c.num_layers; ++l) e->ws_x[l] = w.take(T * H * es);
+    // MAG in front of layer j >= 1: the pre-gate tensor (an engine with the gate behind the embeddings carves exactly what it always did)
+    e->ws_pre = c.injection_index >= 1 ? w.take(T * H * es) : 0;
     e->lw.resize(c.num_layers);
     for (int l = 0; l < c.num_layers; ++l) {
         LayerWs& x = e->lw[l];
@@ -224,6 +228,7 @@ static int prepare_pass(mb_bert_engine* e, int T, hipStream_t st) {
             return (int)hipMemsetAsync(ws + off + (size_t)T * cols * es, 0, (size_t)(Tp - T) * cols * es, st);
         };
         CK(zp(e->ws_emb, H));
+        if (c.injection_index >= 1) CK(zp(e->ws_pre, H));        // the `text` operand of MAG's weight gradient
         CK(mag_clear_pad_rows(dt, ws + e->ws_mag, e->mw, T, H, st));
         for (int k = 0; k < 2; ++k) {
             CK(zp(e->ws_ds[k], H)); CK(zp(e->ws_dzd[k], H)); CK(zp(e->ws_ds2[k], H)); CK(zp(e->ws_dzd2[k], H));
@@ -509,6 +514,7 @@ int mb_bert_create(const mb_bert_config* cfg, mb_bert_engine** out) {
     if (cfg->max_seq > cfg->max_position || cfg->num_labels < 1) return MB_ERR_SHAPE;
     if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return MB_ERR_DTYPE;
     if (cfg->hidden_act < ACT_GELU || cfg->hidden_act > ACT_MISH) return MB_ERR_ARG;
+    if (cfg->injection_index < 0 || cfg->injection_index >= cfg->num_layers) return MB_ERR_ARG;       // MAG sits in front of an existing layer
     mb_bert_engine* e = new mb_bert_engine();
     e->c = *cfg;
     e->read_env();
@@ -584,9 +590,10 @@ int mb_bert_sync_weights(mb_bert_engine* e, void* stream) {
     return MB_OK;
 }
 
-// The forward of layers [l0, l1): `first` = with the pass set-up, the embeddings and MAG in front; `last` = with the pooler, the classifier
-// and the loss behind.  mb_bert_forward is the whole range; the sharded data-parallel step runs it in pieces whose weights arrive by
-// all-gather (csrc/comm.h: cut mode).
+// The forward of layers [l0, l1): `first` = with the pass set-up and the embeddings in front; `last` = with the pooler, the classifier
+// and the loss behind.  MAG runs in front of layer injection_index: in the piece that holds that layer (index 0: behind the embeddings).
+// mb_bert_forward is the whole range; the sharded data-parallel step runs it in pieces whose weights arrive by all-gather
+// (csrc/comm.h: cut mode).
 static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const float* visual, const float* acoustic,
                               const int64_t* attention_mask, const int64_t* token_type_ids, const float* labels, int B, int L,
                               int training, uint64_t seed, uint64_t step, float* logits, float* loss, float* loss_run, void* stream,
@@ -603,20 +610,26 @@ static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const
     float* P = e->P;
     char* ws = e->ws;
     if (first && !e->capturing) CK(prepare_pass(e, T, st));
-    // embeddings (bert.py:211-216)
+    const int inj = c.injection_index;
+    // embeddings (bert.py:211-216); with MAG further up they are what layer 0 reads
     if (first) CK(embed_ln_forward(dt, input_ids, token_type_ids, e->emb_in ? e->emb_in : P + e->word, P + e->pos, P + e->type, P + e->emb_lnw, P + e->emb_lnb,
-                        c.layer_norm_eps, ws + e->ws_emb, (float*)(ws + e->ws_emb_st), (float*)(ws + e->ws_emb_st) + T, B, L,
+                        c.layer_norm_eps, ws + (inj >= 1 ? e->ws_x[0] : e->ws_emb), (float*)(ws + e->ws_emb_st), (float*)(ws + e->ws_emb_st) + T, B, L,
                         H, e->key(SITE_EMB, c.hidden_dropout), st, e->pos_ids));
     // MAG (bert.py:219): packed weights are refreshed every pass (5.5 MB) so optimizer steps are seen -- by a launch here, or, in the
     // single-call step, by extra blocks of the step prologue
-    if (first) CK(mag_fwd_impl(dt, ws + e->ws_emb, visual, acoustic, P + e->mag_whv, P + e->mag_bhv, P + e->mag_wha, P + e->mag_bha,
-                    P + e->mag_wv, P + e->mag_bv, P + e->mag_wa, P + e->mag_ba, P + e->mag_lnw, P + e->mag_lnb,
-                    c.mag_layer_norm_eps, c.beta_shift, e->key(SITE_MAG, c.mag_dropout), ws + e->ws_x[0], ws + e->ws_mag,
-                    e->mw, T, H, c.visual_dim, c.acoustic_dim, !(e->in_step && e->packed_w), st, true, e->in_step && e->packed));
+    auto mag = [&](const char* text, char* out) -> int {
+        return mag_fwd_impl(dt, text, visual, acoustic, P + e->mag_whv, P + e->mag_bhv, P + e->mag_wha, P + e->mag_bha,
+                            P + e->mag_wv, P + e->mag_bv, P + e->mag_wa, P + e->mag_ba, P + e->mag_lnw, P + e->mag_lnb,
+                            c.mag_layer_norm_eps, c.beta_shift, e->key(SITE_MAG, c.mag_dropout), out, ws + e->ws_mag,
+                            e->mw, T, H, c.visual_dim, c.acoustic_dim, !(e->in_step && e->packed_w), st, true, e->in_step && e->packed);
+    };
+    if (first && inj == 0) CK(mag(ws + e->ws_emb, ws + e->ws_x[0]));
     // encoder (bert.py:221-229)
     for (int l = l0; l < l1; ++l) {
         const LayerOff& o = e->lo[l];
         const LayerWs& w = e->lw[l];
+        // the gate in front of this layer: it reads what layer l - 1 wrote (ws_pre) and writes what this layer reads
+        if (l == inj && inj >= 1) CK(mag(ws + e->ws_pre, ws + e->ws_x[l]));
         const char* x = ws + e->ws_x[l];
         CK(gemm(dt, GEMM_NT, EPI_BIAS, T, 3 * H, H, x, H, e->W(o.wqkv), H, ws + w.qkv, 3 * H, nullptr, nullptr, P + o.bqkv,
                 nullptr, 0, kNoDrop, 1, 0, st));
@@ -637,7 +650,7 @@ static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const
                 nullptr, 0, kNoDrop, 1, 0, st, 0, 0, GradAcc{}, c.hidden_act));
         CK(gemm(dt, GEMM_NT, EPI_BIAS_DROP_RES, T, H, I, ws + w.g, I, e->W(o.w2), I, ws + w.s2, H, nullptr, nullptr,
                 P + o.b2, ws + w.y1, H, e->key(SITE_LAYER0 + 4 * l + 2, c.hidden_dropout), 1, 0, st));
-        CK(ln_forward(dt, ws + w.s2, P + o.ln2w, P + o.ln2b, c.layer_norm_eps, ws + e->ws_x[l + 1], (float*)(ws + w.st2),
+        CK(ln_forward(dt, ws + w.s2, P + o.ln2w, P + o.ln2b, c.layer_norm_eps, ws + (l + 1 == inj ? e->ws_pre : e->ws_x[l + 1]), (float*)(ws + w.st2),
                       (float*)(ws + w.st2) + T, T, H, kNoDrop, st, pf2));
     }
     if (!last) return MB_OK;
@@ -838,16 +851,36 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                 CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, st));
             }
             CK(dgrad_ride(EPI_ADD_RES, T, H, 3 * H, dqkv, 3 * H, e->W(o.wqkv), H, dx, H, dsB, H, nullptr));
+            if (l == c.injection_index && l >= 1) {
+                // MAG sits in front of this layer: dx is the gradient of the gate's output.  The gate's backward is the only reader of dx
+                // and runs before the GEMM that forms d_text, so d_text goes back into dx -- the incoming gradient of layer l - 1 -- without
+                // a copy.  (The riders this stage's launches carried took GEMM weights of layers above l; MAG reads none of them.)
+                int mblk = 0;
+                CK(mag_bwd_impl(dt, dx, ws + e->ws_pre, P + e->mag_bhv, P + e->mag_bha, P + e->mag_bv, P + e->mag_ba,
+                                P + e->mag_lnw, c.beta_shift, e->key(SITE_MAG, c.mag_dropout), ws + e->ws_mag, e->mw, dx, nullptr,
+                                nullptr, G + e->mag_whv, G + e->mag_bhv, G + e->mag_wha, G + e->mag_bha, G + e->mag_wv,
+                                G + e->mag_bv, G + e->mag_wa, G + e->mag_ba, G + e->mag_lnw, G + e->mag_lnb, T, H, c.visual_dim,
+                                c.acoustic_dim, true, st, acc, true, (float*)(ws + e->ws_lnp_a) + (size_t)NL * e->lnp_stride,
+                                (float*)(ws + e->ws_lnp_b) + (size_t)NL * e->lnp_stride, &mblk, e->ow_pass));
+                e->mag_nblk = mblk;
+                if (!defer_ln) {         // wherever the layers' own slabs are reduced per stage, MAG's six are reduced right away
+                    float* const m6[6] = {G + e->mag_bhv, G + e->mag_bha, G + e->mag_bv, G + e->mag_ba, G + e->mag_lnw, G + e->mag_lnb};
+                    CK(ln_reduce_partials((const float*)(ws + e->ws_lnp_a) + (size_t)NL * e->lnp_stride,
+                                          (const float*)(ws + e->ws_lnp_b) + (size_t)NL * e->lnp_stride, mblk, H, m6, st, acc));
+                }
+            }
         } else {
-            // ---- MAG + embeddings
+            // ---- MAG (when it sits behind the embeddings) + embeddings
+            const bool mag_here = c.injection_index == 0;
             char* dx = ws + e->ws_dxa;
-            char* de = ws + e->ws_dxb;
+            char* de = mag_here ? ws + e->ws_dxb : dx;       // (MAG further up: layer 0's input gradient is the embeddings' output gradient)
             // single-call step: the six column sums of MAG's gate go to partial slabs like the LayerNorm ones, and ONE launch reduces
             // every layer's and MAG's slabs (nobody needs these small gradients before AdamW)
             const bool defer_ln = e->in_step && !e->stage_mode && NL + 2 <= MB_LN_MAX_LAYERS && NL > 0;
             float* mpa = (float*)(ws + e->ws_lnp_a) + (size_t)NL * e->lnp_stride;
             float* mpb = (float*)(ws + e->ws_lnp_b) + (size_t)NL * e->lnp_stride;
-            int mblk = 0;
+            int mblk = e->mag_nblk;
+            if (mag_here)
             CK(mag_bwd_impl(dt, dx, ws + e->ws_emb, P + e->mag_bhv, P + e->mag_bha, P + e->mag_bv, P + e->mag_ba,
                             P + e->mag_lnw, c.beta_shift, e->key(SITE_MAG, c.mag_dropout), ws + e->ws_mag, e->mw, de, nullptr,
                             nullptr, G + e->mag_whv, G + e->mag_bhv, G + e->mag_wha, G + e->mag_bha, G + e->mag_wv,
@@ -879,7 +912,9 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                     for (int q = 0; q < 6; ++q) dst.d[k - first][q] = d6[q];
                 }
                 float* const m6[6] = {G + e->mag_bhv, G + e->mag_bha, G + e->mag_bv, G + e->mag_ba, G + e->mag_lnw, G + e->mag_lnb};
-                for (int q = 0; q < 6; ++q) dst.d[NL - first][q] = m6[q];
+                // (MAG further up: its slabs wait in slot NL for this launch in the single-call step and were reduced in its own stage otherwise --
+                //  the same slabs in the same order either way)
+                if (mag_here || defer_ln) for (int q = 0; q < 6; ++q) dst.d[NL - first][q] = m6[q];
                 dst.nblk[NL - first] = mblk; dst.nblk[NL + 1 - first] = eblk;         // (their kernels: 8 rows per block; ln_bwd: 16)
                 if (!emb_frozen) { dst.d[NL + 1 - first][0] = G + e->emb_lnw; dst.d[NL + 1 - first][1] = G + e->emb_lnb; }   // (rows 0 / 1 of set a)
                 if (e->pos_ids == nullptr && !emb_frozen) {       // the one-launch embedding backward: token-type sums in row 2 of set a / row 0 of set b
@@ -1124,7 +1159,7 @@ int mb_bert_profile_adamw_us(mb_bert_engine* e, float* us) {
 // ---- optional outputs and the autograd edge of the base model (bert.py:147-156, 227-237)
 const void* mb_bert_hidden_state(const mb_bert_engine* e, int i) {
     if (!e || !e->ws || i < 0 || i > e->c.num_layers) return nullptr;
-    return e->ws + e->ws_x[i];
+    return e->ws + e->ws_x[i];          // the tensor layer i reads: entry injection_index is MAG's output
 }
 int mb_bert_set_attention_output(mb_bert_engine* e, float* probs) {
     if (!e) return MB_ERR_ARG;

@@ -131,7 +131,20 @@ def get_parser():
     parser.add_argument("--hidden_act", type=str, default=None, choices=sorted(_lib_activations()),
                         help="feed-forward activation of either model (BertConfig.hidden_act / XLNetConfig.ff_activation); default: "
                              "what the configuration says (gelu unless a checkpoint's config.json names another)")
+    parser.add_argument("--injection_index", type=int, default=None,
+                        help="apply MAG in front of encoder layer N of either model (0 <= N < number of layers); default: 0 for the "
+                             "BERT models (behind the embeddings, the reference) and XLNET_INJECTION_INDEX for the XLNet models")
     return parser
+
+
+def injection_index_of(a):
+    """--injection_index, or the model's default position of the gate"""
+    if a.injection_index is not None:
+        return a.injection_index
+    if a.model in BERT_MODELS:
+        return 0
+    from .global_configs import XLNET_INJECTION_INDEX
+    return XLNET_INJECTION_INDEX
 
 
 def _lib_activations():
@@ -417,28 +430,29 @@ def prep_for_training(num_train_optimization_steps: int):
     multimodal_config = MultimodalConfig(beta_shift=args.beta_shift, dropout_prob=args.dropout_prob)
     V, A = _dims()
     dt = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
+    inj = injection_index_of(args)
     if args.model in BERT_MODELS:
         if args.pretrained:
             # (the checkpoint directory's config.json names the model size; without one: this --model's configuration)
             from .bert import read_config_beside
             model = MAG_BertForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt, max_seq_length=args.max_seq_length,
+                compute_dtype=dt, max_seq_length=args.max_seq_length, injection_index=inj,
                 config=with_hidden_act(read_config_beside(args.pretrained, 1) or bert_config(args.model), args.hidden_act))
         else:       # offline: fresh init by the reference's init law
             model = MAG_BertForSequenceClassification(with_hidden_act(bert_config(args.model), args.hidden_act), multimodal_config, visual_dim=V,
-                                                      acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
+                                                      acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length, injection_index=inj)
     elif args.model in XLNET_MODELS:
         from .xlnet import MAG_XLNetForSequenceClassification, read_xlnet_config_beside
         if args.pretrained:
             # (the checkpoint directory's config.json names the model size; without one: this --model's configuration)
             model = MAG_XLNetForSequenceClassification.from_pretrained(
                 args.pretrained, multimodal_config=multimodal_config, num_labels=1, visual_dim=V, acoustic_dim=A,
-                compute_dtype=dt, max_seq_length=args.max_seq_length,
+                compute_dtype=dt, max_seq_length=args.max_seq_length, injection_index=inj,
                 config=with_hidden_act(read_xlnet_config_beside(args.pretrained, 1) or xlnet_config(args.model), args.hidden_act))
         else:
             model = MAG_XLNetForSequenceClassification(with_hidden_act(xlnet_config(args.model), args.hidden_act), multimodal_config, visual_dim=V,
-                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length)
+                                                       acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length, injection_index=inj)
     model.to(_device())
     if args.freeze_layers > 0 or args.freeze_embeddings:
         # the common fine-tuning recipe: the groups below leave the frozen parameters out, and the single-call step skips their work

@@ -277,7 +277,7 @@ class AdamW(torch.optim.Optimizer):
             pieces += [(core, a, b) for a, b in merged]
         loose = [it[2] for it in self._plan if it[0] != "flat" and it[2].grad is not None]
 
-        def call(core, a, b):
+        def call(core, a, b, sumsq=False):
             n = b - a
             need = L.mb_grad_clip_scratch_bytes(n)
             scratch = getattr(core, "_clip_scratch", None)
@@ -286,18 +286,25 @@ class AdamW(torch.optim.Optimizer):
                 core._clip_out = torch.empty(2, dtype=torch.float32, device=core.grads.device)
             _lib.check(L.mb_grad_clip_coef(core.grads.data_ptr() + 4 * a, n, max_norm, self.grad_scale, scratch.data_ptr(),
                                            core._clip_out.data_ptr(), core.stream()))
+            if sumsq:       # the piece's sum of squares in double: the launch's per-block partials are still in the scratch
+                return float(scratch[: need // 8].sum())
             norm, coef = core._clip_out.cpu().tolist()          # the one host sync of this path
             return norm, coef
 
         if len(pieces) == 1 and not loose:
             return call(*pieces[0])
+        # Several pieces (frozen tensors between them): their sums of squares are combined in double and the coefficient is formed as
+        # grad_clip_finalize forms it -- norm = grad_scale * sqrt(sum), coef = (float)min(1, (double)max_norm / (norm + 1e-6)) -- so
+        # it is the float the single-call step computes over the same pieces unless the two double sums, which differ in summation
+        # order only, straddle a rounding boundary of that float.  (Piece norms rounded to float each lost that: 7e-8 relative.)
         total = 0.0
         for piece in pieces:
-            total += call(*piece)[0] ** 2
+            total += call(*piece, sumsq=True)
         for p in loose:
-            total += float(p.grad.detach().double().pow(2).sum()) * float(self.grad_scale) ** 2
-        norm = math.sqrt(total)
-        return norm, float(np.float32(min(1.0, max_norm / (norm + 1e-6))))
+            total += float(p.grad.detach().double().pow(2).sum())
+        norm = float(np.float32(self.grad_scale)) * math.sqrt(total)
+        c = float(np.float32(max_norm)) / (norm + 1e-6)
+        return norm, float(np.float32(1.0 if c > 1.0 else c))
 
     # -- planning: map groups onto contiguous flat ranges ------------------------------------------------
     def _build_plan(self):

@@ -196,6 +196,12 @@ typedef struct {
     int dtype;       /* MB_DT_* */
     int max_batch, max_seq;      /* max_seq <= min(512, max_position); above 128 the attention runs the tiled kernels and the
                                     workspace holds their row statistics (engines of max_seq <= 128 carve exactly what they did) */
+    int injection_index;         /* MAG is applied in front of encoder layer `injection_index`: 0 (what a zero-initialised config has always
+                                    run, and the reference) = embeddings -> MAG -> layers; j >= 1 = the embeddings feed layers 0 .. j-1 and
+                                    MAG(output of layer j-1, visual, acoustic) is what layer j reads.  Parameters, names, flat layout and
+                                    dropout sites are the same for every value; the workspace grows by one [T_pad][H] tensor for j >= 1.
+                                    Outside [0, num_layers): MB_ERR_ARG.  (Added after hidden_act, which stays the struct's last field:
+                                    tests/test_activations_cpu.py pins that; set the fields by name) */
     int hidden_act;              /* MB_ACT_*: the activation of BertIntermediate (config.hidden_act); 0 = erf-GELU, what a zero-initialised
                                     config has always run.  Fixed at create time; any other value: MB_ERR_ARG */
 } mb_bert_config;
@@ -227,7 +233,10 @@ int mb_bert_forward(mb_bert_engine* e, const int64_t* input_ids, const float* vi
 /* backward of the last forward.  dlogits fp32 [B][num_labels], or NULL to use the fused MSE gradient
  * 2*(logit-label)/(B*num_labels)*loss_scale.  Gradients are ACCUMULATED into the bound flat grad buffer.
  * stage_begin/stage_end select a sub-range of [0, num_layers+2): 0 = head+pooler, 1..num_layers = encoder layers
- * (last layer first), num_layers+1 = MAG + embeddings -- lets the caller interleave gradient all-reduces. */
+ * (last layer first), num_layers+1 = MAG + embeddings -- lets the caller interleave gradient all-reduces.
+ * With injection_index = j >= 1 the MAG backward runs at the end of stage num_layers - j (behind layer j's input gradient) and
+ * stage num_layers+1 is the embedding backward alone; MAG's gradients are complete when stage num_layers+1 returns, as for
+ * j = 0 (mb_bert_stage_grad_ranges does not depend on j).  The input-gradient chain always runs down to the embeddings. */
 int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* labels, float loss_scale, int stage_begin,
                      int stage_end, void* stream);
 /* activations for API parity (device pointers into the workspace, valid until the next forward) */
@@ -236,7 +245,9 @@ const float* mb_bert_pooled_output(const mb_bert_engine* e);    /* [B][H] fp32 (
 /* Optional outputs of MAG_BertModel.forward (bert.py:147-156, 227-237).
  * hidden_state(i), i in [0, num_layers]: the encoder's all_hidden_states entry i -- i = 0 is the fused embedding MAG returns,
  * i = l + 1 the output of layer l -- [B*L][H] in dtype, valid until the next forward (they are the activations saved for
- * the backward anyway).  set_attention_output: the next forwards also write every layer's attention probabilities AFTER
+ * the backward anyway).  For every injection_index entry i < num_layers is THE TENSOR LAYER i READS: with injection_index = j >= 1
+ * entry 0 is the plain embedding output and entry j is MAG's output (not the output of layer j-1 that MAG read).  This differs from
+ * mb_xlnet_hidden_state, whose list holds the tensor in front of the gate because its reference collects it there.  set_attention_output: the next forwards also write every layer's attention probabilities AFTER
  * dropout (what BertSelfAttention returns with output_attentions) to probs [num_layers][B][nh][L][L] fp32; NULL turns it off. */
 const void* mb_bert_hidden_state(const mb_bert_engine* e, int i);
 int mb_bert_set_attention_output(mb_bert_engine* e, float* probs);

@@ -22,6 +22,7 @@
 //            (mb_*_set_update_frozen): no weight-gradient launch for those layers, no embedding backward; composes with --layer_decay and
 //            --max_grad_norm.  Without --layer_decay the rest is the two parameter groups as a two-class map.  Prints mb_*_freeze_stats.
 //   --act gelu|relu|swish|silu|gelu_new|mish: the feed-forward activation (mb_bert_config.hidden_act / mb_xlnet_config.ff_activation)
+//   --inject N: MAG in front of encoder layer N (injection_index of either config; default 0 for MAG-BERT, 1 for MAG-XLNet)
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
 // Prints one line per run: ms/step (HIP events around the K timed steps), host enqueue ms/step, samples/s, final loss.
@@ -50,7 +51,7 @@ int main(int argc, char** argv) {
     int steps = 30, warmup = 5, B = 48, L = 50, V = 47, A = 74, layers = 12, graph = 0, h2d = 0, nbatch = 4, dtype = MB_DT_BF16;
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
     double layer_decay = 1.0, head_lr_mult = 1.0, max_grad_norm = 0.0;
-    int freeze_layers = 0, freeze_emb = 0, act = MB_ACT_GELU;
+    int freeze_layers = 0, freeze_emb = 0, act = MB_ACT_GELU, inject = -1;      // --inject N: MAG in front of layer N (default: 0 | MAG-XLNet: 1)
     const char* act_name = "gelu";
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
@@ -65,6 +66,7 @@ int main(int argc, char** argv) {
         else if (k == "--layer_decay") layer_decay = atof(v); else if (k == "--head_lr_mult") head_lr_mult = atof(v);
         else if (k == "--max_grad_norm") max_grad_norm = atof(v);
         else if (k == "--freeze_layers") freeze_layers = atoi(v); else if (k == "--freeze_emb") freeze_emb = atoi(v);
+        else if (k == "--inject") inject = atoi(v);
         else if (k == "--act") {
             const char* names[] = {"gelu", "relu", "swish", "gelu_new", "mish"};
             act = strcmp(v, "silu") == 0 ? MB_ACT_SWISH : -1;
@@ -74,7 +76,7 @@ int main(int argc, char** argv) {
         }
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --inject)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -83,7 +85,7 @@ int main(int argc, char** argv) {
     c.max_position = 512; c.type_vocab = 2; c.num_labels = 1; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
     c.layer_norm_eps = 1e-12f; c.mag_layer_norm_eps = 1e-5f; c.beta_shift = 1.0f;
     c.hidden_dropout = 0.1f; c.attn_dropout = 0.1f; c.mag_dropout = 0.5f; c.dtype = dtype; c.max_batch = B; c.max_seq = L;
-    c.hidden_act = act;
+    c.hidden_act = act; c.injection_index = inject < 0 ? 0 : inject;
     mb_bert_engine* e = nullptr;
     mb_xlnet_engine* ex = nullptr;
     size_t n, nd, wsb, shb, she;
@@ -91,7 +93,7 @@ int main(int argc, char** argv) {
         if (!graph || dp) { fprintf(stderr, "--model xlnet: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
         mb_xlnet_config xc = {};
         xc.vocab_size = 32000; xc.d_model = hidden; xc.n_layer = layers; xc.n_head = heads; xc.d_inner = inter; xc.num_labels = 1;
-        xc.visual_dim = V; xc.acoustic_dim = A; xc.injection_index = 1;
+        xc.visual_dim = V; xc.acoustic_dim = A; xc.injection_index = inject < 0 ? 1 : inject;
         xc.layer_norm_eps = 1e-12f; xc.mag_layer_norm_eps = 1e-5f; xc.beta_shift = 1.0f;
         xc.dropout = 0.1f; xc.summary_last_dropout = 0.1f; xc.mag_dropout = 0.5f; xc.dtype = dtype; xc.max_batch = B; xc.max_seq = L;
         xc.ff_activation = act;
