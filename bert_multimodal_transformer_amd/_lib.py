@@ -116,6 +116,10 @@ PROTOTYPES = {
     "mb_debug_gemm_grouped_ex": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                       _sz, _i, _i, _f, _f, _f, _f, _f, _i, _i, _f, _vp, _vp]),
     "mb_debug_gemm_last_kernel": (_i, [C.c_char_p, _i]),
+    "mb_debug_gemm_grouped_rows": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mb_debug_live_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mb_bert_debug_live_wgrad_launches": (_i, [_vp]),
+    "mb_bert_debug_wgrad_dy": (_vp, [_vp, _i, _i, C.POINTER(_i)]),
     "mb_debug_gemm_trace": (_i, [_vp, _i]),
     "mb_debug_attention_trace": (_i, [_vp, _i]),
     "mb_xlnet_attention_probs": (_vp, [_vp, _i, C.POINTER(_i)]),

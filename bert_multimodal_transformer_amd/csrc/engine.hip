@@ -17,6 +17,11 @@
 
 // ================================================================================================ engine
 struct LayerOff { size_t wqkv, wo, w1, w2, bqkv, bo, ln1w, ln1b, b1, b2, ln2w, ln2b; };
+// MB_WGRAD_LIVE_ROWS when unset (not in deterministic mode): see StepMixin::live_mode.  1: the [CLS]-row list of mode 2 measured inside
+// the spread (3.095-3.104 ms without, 3.090-3.102 with, five alternations: profiles/wgrad_live_rows.txt), so it stays out of the default
+#ifndef MB_WGRAD_LIVE_DEFAULT
+#define MB_WGRAD_LIVE_DEFAULT 1
+#endif
 struct LayerWs { size_t qkv, ctx, s1, st1, y1, u, g, s2, st2, stats; };     // stats: tiled attention's row statistics (max_seq > 128 only)
 
 struct mb_bert_engine : StepMixin {
@@ -204,6 +209,17 @@ static void build_layout(mb_bert_engine* e) {
     e->stamp_rows = (size_t)c.vocab_size;
     e->stamp_off = w.take(((size_t)c.vocab_size + 2) * 4);
     e->stamp_enable = env_on("MB_ADAMW_SKIP_ZERO_ROWS", true);
+    // the live-row list of a batch + its count word (StepMixin::live_built; MB_WGRAD_LIVE_ROWS=0: dense weight gradients); bf16 only
+    if (c.dtype == DT_BF16) {
+        e->live_cap = std::max((size_t)192, T);
+        e->live_off = w.take(2 * (e->live_cap + 8) * 4);          // (the live rows, then the [CLS] rows)
+        // Deterministic mode promises the bits of the python-driven passes, whose weight gradients stay dense: a sum over the listed
+        // rows groups the same products differently (same bits from run to run, other bits than the dense sum), so there the
+        // default is off and MB_WGRAD_LIVE_ROWS=1 asks for it by name.
+        e->live_mode = env_int("MB_WGRAD_LIVE_ROWS", e->deterministic ? 0 : MB_WGRAD_LIVE_DEFAULT);
+        if (e->live_mode < 0 || e->live_mode > 2) e->live_mode = MB_WGRAD_LIVE_DEFAULT;
+        e->live_enable = e->live_mode > 0;
+    }
     e->one_sweep = env_on("MB_ADAMW_ONE_SWEEP", true);
     if (e->deterministic) {          // shadow accumulator of everything behind the layers' GEMM weights (those have ONE writer per element)
         e->det_begin = e->wp; e->det_end = e->n_params;
@@ -359,6 +375,33 @@ int mb_debug_gemm_grouped_ex(int dtype, int count, const int* M, const int* N, i
     if (int e = debug_ride(ride, rp, rg, rm, rv, rshadow, n4, blocks, zero_grad,
                            adam_scalars(lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale), adam_dev, st)) return e;
     return gemm_grouped_tn_launch(dtype, g, count, tile, st, stages, ride.blocks > 0 ? &ride : nullptr);
+}
+
+int mb_debug_gemm_grouped_rows(int dtype, int count, const int* M, const int* N, int K, const void* const* dY, const int* ldy,
+                               const void* const* X, const int* ldx, float* const* dW, const int* ldw, const int* overwrite, int tile,
+                               const void* const* rows, const void* const* nrows, void* stream) {
+    if (count < 1 || count > MB_MAX_GROUP || !M || !N || !dY || !X || !dW || !ldy || !ldx || !ldw || !rows || !nrows) return MB_ERR_ARG;
+    GemmArgs g[MB_MAX_GROUP];
+    GroupedRows lr = {};
+    for (int i = 0; i < count; ++i) {
+        g[i] = wgrad_args(M[i], N[i], K, dY[i], ldy[i], X[i], ldx[i], dW[i], ldw[i]);
+        g[i].overwrite = overwrite ? overwrite[i] : 0;
+        lr.rows[i] = (const uint32_t*)rows[i]; lr.nrows[i] = (const uint32_t*)nrows[i];
+    }
+    if (!gemm_grouped_tn_ok(dtype, g, count, tile)) return MB_ERR_SHAPE;
+    return gemm_grouped_tn_launch(dtype, g, count, tile, (hipStream_t)stream, 0, nullptr, &lr);
+}
+
+int mb_bert_debug_live_wgrad_launches(const mb_bert_engine* e) { return e ? e->live_launches : -1; }
+
+int mb_debug_live_rows(const int64_t* mask, int B, int L, int Tp, void* live_rows, void* live_count, void* cls_rows, void* cls_count,
+                       void* stream) {
+    if (!mask || !live_rows || !live_count || B < 1 || L < 1) return MB_ERR_ARG;
+    PrologueArgs pa = {};
+    pa.live_rows = (uint32_t*)live_rows; pa.live_count = (uint32_t*)live_count; pa.live_mask = mask;
+    pa.live_T = B * L; pa.live_Tp = Tp; pa.live_L = L;
+    pa.cls_rows = (uint32_t*)cls_rows; pa.cls_count = (uint32_t*)cls_count;
+    return step_prologue(pa, (hipStream_t)stream);
 }
 
 int mb_debug_gemm_last_kernel(char* out, int cap) { return gemm_last_kernel(out, cap); }
@@ -832,6 +875,10 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                                   e->head_mask ? e->head_mask + (size_t)l * nh : nullptr, acc, ra.blocks ? &ra : nullptr,
                                   e->attn_stats(w)));
             // riders: an optimizer update in the empty slots of this launch (take_ride, below the loop header)
+            // single-call step, 256 x 128 tiles: the sums run over the live token rows the prologue listed (a padding token's row of
+            // every dY is exactly zero); anything else -- explicit and stage-driven passes, the other tiles -- stays dense
+            const bool live = grouped && e->live_built && e->in_step && !e->stage_mode && wtile == 256 && Tk <= (int)e->live_cap &&
+                              gemm_grouped_gather_ok(dt, wtile);
             AdamRide ride = {};
             if (grouped && !wfrozen) {
                 int tiles = 0;
@@ -840,12 +887,29 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
                 const int slots = e->cu_count() * (wtile == 256 ? 1 : wtile == 128 ? 2 : 0);
                 // what 40 CUs stream while the tiles multiply (~41 GB/s per CU; same-box sweeps in profiles/r06_adamw_ride_budget.txt,
                 // r06_adamw_ride_ab.txt: 2.5 M parameters at T = 2400, 3.5 M at T = 4096; more stretches the launch)
-                const size_t budget = e->ride_params > 0 ? (size_t)e->ride_params : std::min((size_t)1000 * (size_t)Tk, (size_t)1100000 + (size_t)590 * (size_t)Tk);
+                // (live rows: the tiles of a padded batch finish ~8 us sooner and the riders set the launch's length -- same-box scans at
+                //  T = 2400: 3.14 ms at 0.6 M | 3.11 at 1.2 M | 3.09 at 1.5 M (this) | 3.09 at 1.8 M | 3.13 at 2.1 M | 3.18 at 2.43 M; T = 4096: 4.33
+                //  at 1 M | 4.31 at 1.5 M | 4.33 at 2 M (this: flat within 0.4 % from 1 M to 2.5 M) | 4.33 at 2.5 M | 4.35 at 3.5 M.  The line goes through
+                //  those two points and is switched by the path, not by how many rows are live -- the host does not know that --, so an all-live
+                //  batch pays the small budget: +0.4 % at B = 48, L = 50: profiles/wgrad_live_rows.txt)
+                const size_t dense_budget = std::min((size_t)1000 * (size_t)Tk, (size_t)1100000 + (size_t)590 * (size_t)Tk);
+                const size_t budget = e->ride_params > 0 ? (size_t)e->ride_params
+                                    : live ? std::min(dense_budget, (size_t)770000 + (size_t)300 * (size_t)Tk) : dense_budget;
                 ride = take_ride(l, budget, e->ride_blocks > 0 ? e->ride_blocks : (slots - tiles) / 8 * 8);
             }
             if (grouped) {
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l], st));
-                if (!wfrozen) CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, ride.blocks ? &ride : nullptr));
+                GroupedRows lr = {};
+                if (live) {
+                    for (int i = 0; i < 4; ++i) { lr.rows[i] = e->live_rows(ws); lr.nrows[i] = e->live_count(ws); }
+                    // the top layer: the head reads hidden[:, 0], so the dY of its ffn2, ffn1 and out-proj problems is non-zero on the
+                    // [CLS] rows only (LayerNorm, dropout and the dgrads are row-wise); its qkv problem keeps the live rows (dK, dV)
+                    if (e->live_mode >= 2 && l == NL - 1)
+                        for (int i = 0; i < 3; ++i) { lr.rows[i] = e->cls_rows(ws); lr.nrows[i] = e->cls_count(ws); }
+                    lr.note = (e->live_mode >= 2 && l == NL - 1) ? "rows=cls,cls,cls,live" : "rows=live";
+                    if (!wfrozen) ++e->live_launches;
+                }
+                if (!wfrozen) CK(gemm_grouped_tn_launch(dt, wg, 4, wtile, st, 0, ride.blocks ? &ride : nullptr, live ? &lr : nullptr));
                 if (e->prof) CK((int)hipEventRecord(e->pev[2 * l + 1], st));
             } else if (!wfrozen) {
                 CK(wgrad(dt, 3 * H, H, Tk, dqkv, 3 * H, ws + e->ws_x[l], H, G + o.wqkv, H, st));
@@ -1160,6 +1224,23 @@ int mb_bert_profile_adamw_us(mb_bert_engine* e, float* us) {
 const void* mb_bert_hidden_state(const mb_bert_engine* e, int i) {
     if (!e || !e->ws || i < 0 || i > e->c.num_layers) return nullptr;
     return e->ws + e->ws_x[i];          // the tensor layer i reads: entry injection_index is MAG's output
+}
+const void* mb_bert_debug_wgrad_dy(const mb_bert_engine* e, int layer, int which, int* ld) {
+    if (!e || !e->ws || layer < 0 || layer >= e->c.num_layers || which < 0 || which > 7) return nullptr;
+    const int par = layer & 1, H = e->c.hidden_size, I = e->c.intermediate_size;
+    const bool hd = e->training && e->c.hidden_dropout > 0.f;
+    if (ld) *ld = (which == 1 || which == 4) ? I : which == 3 ? 3 * H : H;
+    const LayerWs& w = e->lw[layer];
+    switch (which) {
+        case 4: return e->ws + w.g;
+        case 5: return e->ws + w.y1;
+        case 6: return e->ws + w.ctx;
+        case 7: return e->ws + e->ws_x[layer];
+        case 0: return e->ws + (hd ? e->ws_dzd[par] : e->ws_ds[par]);
+        case 1: return e->ws + e->ws_du[par];
+        case 2: return e->ws + (hd ? e->ws_dzd2[par] : e->ws_ds2[par]);
+        default: return e->ws + e->ws_dqkv[par];
+    }
 }
 int mb_bert_set_attention_output(mb_bert_engine* e, float* probs) {
     if (!e) return MB_ERR_ARG;

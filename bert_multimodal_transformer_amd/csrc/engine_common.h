@@ -259,6 +259,18 @@ struct StepMixin {
     // single-call step: the prologue counts the occurrences of every token id (workspace offset of the table, 0 = none); `counted`
     // tells the engine's backward that the table describes the batch of this step
     size_t idcnt_off = 0; bool idcnt_enable = false, counted = false;
+    // Live token rows (kernels.h PrologueArgs::live_rows; MB_WGRAD_LIVE_ROWS=0: off): the single-call step's prologue lists the rows of the
+    // batch whose mask is set, and the layers' grouped weight gradients sum over those rows only (the dY row of a padding token is
+    // exactly zero in every layer).  live_off: workspace offset of the list, live_cap entries, the count word behind them; 0 = the engine
+    // carves none.  live_built: this step's prologue wrote the list (cleared with in_step).
+    // live_mode (MB_WGRAD_LIVE_ROWS): 0 dense | 1 the live rows in every launch | 2 also the [CLS]-row list (PrologueArgs::cls_rows, a
+    // second list of the same size behind the first) for the top layer's out-proj / ffn1 / ffn2 problems.  live_launches: gathered
+    // weight-gradient launches the last single-call step enqueued (test hook).
+    size_t live_off = 0, live_cap = 0; bool live_enable = false, live_built = false; int live_mode = 0, live_launches = 0;
+    uint32_t* live_rows(char* ws) const { return (uint32_t*)(ws + live_off); }
+    uint32_t* live_count(char* ws) const { return live_rows(ws) + live_cap; }
+    uint32_t* cls_rows(char* ws) const { return live_rows(ws) + live_cap + 8; }
+    uint32_t* cls_count(char* ws) const { return cls_rows(ws) + live_cap; }
     // Untouched word rows (kernels.h WordSkip; MB_ADAMW_SKIP_ZERO_ROWS=0: off).  stamp_off: workspace offset of the vocab-sized stamp table
     // followed by the two state words (0 = this engine has none); sweep_no: the number of the next optimizer update, counted on the host
     // (train_step_impl runs for every step, replayed or not) and never 0, the table's initial value.
@@ -749,6 +761,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (e->any_frozen && variant > 0) return MB_ERR_MODE;
     if (e->any_frozen && variant == 0) variant = -e->map_version;
     e->upd_ridden = e->upd_swept = 0; e->upd_segments = 0;
+    e->live_launches = 0;
     e->frz_elems = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
     if (e->any_frozen && e->frz_dirty) CK(e->clear_frozen(e->G, st));
     if (m && e->n_classes > 0) CK(e->ensure_class_table());
@@ -766,7 +779,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     struct Flags {
         E* e; bool ok, with_opt, stale_before;
         ~Flags() {
-            e->in_step = false; e->loss_cleared = false; e->packed = false; e->packed_w = false; e->counted = false;
+            e->in_step = false; e->loss_cleared = false; e->packed = false; e->packed_w = false; e->counted = false; e->live_built = false;
             if (ok && e->clip_step) e->clip_ran = true;
             e->clip_step = false;
             e->grads_zero = ok && with_opt;
@@ -801,6 +814,14 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (e->idcnt_enable && ids && !no_embed) { pa.ids = (const int64_t*)ids; pa.n_ids = B * L; pa.id_count = (int*)(ws + e->idcnt_off); }
     e->counted = pa.id_count != nullptr;
     if (stamping) { pa.stamp = e->stamp_table(ws); pa.stamp_state = e->stamp_state(ws); pa.stamp_no = e->sweep_no; pa.stamp_on = e->stamp_live ? 1u : 0u; }
+    // live token rows for the weight gradients (not the data-parallel variants: they stay dense)
+    if (e->live_off != 0 && e->live_enable && variant <= 0 && mask != nullptr && (size_t)align_up((size_t)B * L, 64) <= e->live_cap &&
+        B <= MB_LIVE_MAX_SAMPLES && B * L <= MB_LIVE_MAX_ROWS) {
+        pa.live_rows = e->live_rows(ws); pa.live_count = e->live_count(ws); pa.live_mask = (const int64_t*)mask;
+        pa.live_T = B * L; pa.live_Tp = (int)align_up((size_t)B * L, 64); pa.live_L = L;
+        if (e->live_mode >= 2) { pa.cls_rows = e->cls_rows(ws); pa.cls_count = e->cls_count(ws); }
+        e->live_built = true;
+    }
     if (m) {
         double ss = lr;
         if (correct_bias) ss = (double)lr * sqrt(1.0 - pow((double)beta2, (double)opt_step)) / (1.0 - pow((double)beta1, (double)opt_step));

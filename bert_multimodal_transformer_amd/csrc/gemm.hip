@@ -642,13 +642,14 @@ int gemm_last_kernel(char* out, int cap) {
     return (int)strlen(out);
 }
 
-void gemm_log(const void* fn, hipStream_t st, const GemmArgs* p, int count) {
+void gemm_log(const void* fn, hipStream_t st, const GemmArgs* p, int count, const char* note) {
     g_last_kernel = fn;
     if (!host_env().log) return;
     double fl = 0.0;
     for (int i = 0; i < count; ++i) fl += 2.0 * (double)p[i].M * (double)p[i].N * (double)p[i].K;
     const char* name = hipKernelNameRefByPtr(fn, st);
-    fprintf(stderr, "[magbert gemm] %s problems=%d flop=%.0f M=%d N=%d K=%d\n", name ? name : "?", count, fl, p[0].M, p[0].N, p[0].K);
+    fprintf(stderr, "[magbert gemm] %s problems=%d flop=%.0f M=%d N=%d K=%d%s%s\n", name ? name : "?", count, fl, p[0].M, p[0].N, p[0].K,
+            note ? " " : "", note ? note : "");
 }
 
 void gemm_log_ride(const AdamRide& r) {
@@ -939,11 +940,20 @@ static int launch_T(const GemmArgs& a, int layout, int mode, int splits, int til
 }
 
 template <class T, int BM, int BN>
-static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int stages, const AdamRide* ride) {
+static int launch_grouped(const GemmArgs* probs, int count, hipStream_t st, int stages, const AdamRide* ride, const GroupedRows* rows) {
     constexpr int BKE = 128 / sizeof(T);
     constexpr int EPV = 16 / sizeof(T);
     GroupedGemmArgs ga;
     ga.count = count;
+    bool gather = false;
+    for (int i = 0; i < MB_MAX_GROUP; ++i) {
+        ga.rows[i] = rows && i < count ? rows->rows[i] : nullptr;
+        ga.nrows[i] = rows && i < count ? rows->nrows[i] : nullptr;
+        gather = gather || ga.rows[i] != nullptr;
+    }
+    ga.note = rows ? rows->note : nullptr;
+    // only the 256 x 128 ping-pong kernel has the gathered loop: a list anywhere else is an error, not a dense launch
+    if (gather && !(BM == 256 && sizeof(T) == 2 && host_env().group_big == 2)) return MB_ERR_MODE;
     ga.ride = AdamRide{};
     if (ride && ride->blocks > 0 && ride->n4 > 0) {
         if (ride->blocks % 8 || BM < 128) return MB_ERR_ARG;
@@ -1026,11 +1036,14 @@ int gemm_grouped_tn_ok(int dtype, const GemmArgs* probs, int count, int tile) {
     return 1;
 }
 
-int gemm_grouped_tn_launch(int dtype, const GemmArgs* probs, int count, int tile, hipStream_t st, int stages, const AdamRide* ride) {
+int gemm_grouped_gather_ok(int dtype, int tile) { return dtype == DT_BF16 && tile == 256 && host_env().group_big == 2 ? 1 : 0; }
+
+int gemm_grouped_tn_launch(int dtype, const GemmArgs* probs, int count, int tile, hipStream_t st, int stages, const AdamRide* ride,
+                           const GroupedRows* rows) {
     if (count < 1 || count > MB_MAX_GROUP) return MB_ERR_ARG;
-    if (dtype == DT_BF16 && tile == 256) return launch_grouped<bf16, 256, 128>(probs, count, st, stages, ride);
-    if (dtype == DT_BF16) return tile == 128 ? launch_grouped<bf16, 128, 128>(probs, count, st, stages, ride) : launch_grouped<bf16, 64, 64>(probs, count, st, stages, ride);
-    if (dtype == DT_F32) return tile == 128 ? launch_grouped<float, 128, 128>(probs, count, st, stages, ride) : launch_grouped<float, 64, 64>(probs, count, st, stages, ride);
+    if (dtype == DT_BF16 && tile == 256) return launch_grouped<bf16, 256, 128>(probs, count, st, stages, ride, rows);
+    if (dtype == DT_BF16) return tile == 128 ? launch_grouped<bf16, 128, 128>(probs, count, st, stages, ride, rows) : launch_grouped<bf16, 64, 64>(probs, count, st, stages, ride, rows);
+    if (dtype == DT_F32) return tile == 128 ? launch_grouped<float, 128, 128>(probs, count, st, stages, ride, rows) : launch_grouped<float, 64, 64>(probs, count, st, stages, ride, rows);
     return MB_ERR_DTYPE;
 }
 

@@ -99,7 +99,15 @@ struct GroupedGemmArgs {
     int count;
     int chunk;                      // > 0: tiles per XCD of the group-wide XCD-compact placement (gemm.hip); 0: per-problem regions
     AdamRide ride;                  // ride.blocks > 0: that many workgroups in front of the tiles run an optimizer update instead
+    // Gathered k loop (the 256 x 128 ping-pong kernel only): problem i sums over the k rows rows[i][0 .. n) of BOTH operands, in list order,
+    // n = min(K, *nrows[i]) -- read by the kernel, a multiple of 64 and at least 192; the list holds at least that many valid entries
+    // (< K).  rows[i] == null: the dense loop over all K rows.
+    const uint32_t* rows[MB_MAX_GROUP];
+    const uint32_t* nrows[MB_MAX_GROUP];
+    const char* note;               // host only: what the launch's MB_GEMM_LOG line says about the lists (may be null)
 };
+// the row lists of a gathered grouped launch, per problem (null = dense)
+struct GroupedRows { const uint32_t* rows[MB_MAX_GROUP]; const uint32_t* nrows[MB_MAX_GROUP]; const char* note; };      // note: for the MB_GEMM_LOG line
 // A dgrad launch (GEMM_NN; mode EPI_ADD_RES or EPI_DGELU) with riders: gemm_nn_ride_tiles -> the tile count (padded to 8) of the launch
 // gemm_launch would make of `a` when that is one of the two kernels that leave block slots free (64 x 64 three-slot, 128 x 128 two-slot;
 // *per_cu = block slots per CU), else 0; gemm_nn_ride_launch: that launch with ride.blocks (a multiple of 8) rider workgroups behind the
@@ -108,7 +116,9 @@ int gemm_nn_ride_tiles(int dtype, int mode, const GemmArgs& a, int* per_cu);
 int gemm_nn_ride_launch(int dtype, int mode, const GemmArgs& a, const AdamRide& ride, hipStream_t st);
 int gemm_grouped_tn_ok(int dtype, const GemmArgs* probs, int count, int tile);
 int gemm_grouped_tn_launch(int dtype, const GemmArgs* probs, int count, int tile, hipStream_t st, int stages = 0,
-                           const AdamRide* ride = nullptr);   // stages: 0 = MB_GROUP_STAGES, 4 | 5 = deeper ring (64 x 64 tiles only)
+                           const AdamRide* ride = nullptr,    // stages: 0 = MB_GROUP_STAGES, 4 | 5 = deeper ring (64 x 64 tiles only)
+                           const GroupedRows* rows = nullptr);      // gathered k loop; MB_ERR_MODE where gemm_grouped_gather_ok says 0
+int gemm_grouped_gather_ok(int dtype, int tile);      // 1: a grouped launch of this dtype and tile runs the kernel that takes row lists
 
 // ------------------------------------------------------------------------------------------ row kernels (rowops.hip)
 // LayerNorm over the last dim H (H % 256 == 0, H <= 1024): y = (x-mean)*rstd*gamma + beta ; optional dropout on y.
@@ -348,6 +358,8 @@ int grad_clip_finalize(const double* partial, unsigned blocks, const float* dyn,
 // dropout keys of every site for (seed, step) -- same derivation as make_key() on the host -- and the AdamW scalars of the
 // two parameter groups (lr, bias-corrected step size, gradient scale), or of every update class of a classed step.
 #define MB_PROLOGUE_MAX_COPIES 8
+#define MB_LIVE_MAX_SAMPLES 8192
+#define MB_LIVE_MAX_ROWS 65536
 struct PrologueArgs {
     const uint32_t* src[MB_PROLOGUE_MAX_COPIES]; uint32_t* dst[MB_PROLOGUE_MAX_COPIES]; uint32_t dwords[MB_PROLOGUE_MAX_COPIES];
     int ncopies;
@@ -365,6 +377,18 @@ struct PrologueArgs {
     // stamp[ids[i]] = stamp_no, the number of the optimizer update that will consume this batch's gradients, and stamp_state[0 .. 1] =
     // {stamp_no, stamp_on} for the sweep of that update (WordSkip above); never cleared, right under graph replay.  May be null
     uint32_t* stamp; uint32_t* stamp_state; uint32_t stamp_no, stamp_on;
+    // the live token rows of this batch for the gathered weight gradients (GroupedGemmArgs::rows), built by ONE extra block from the
+    // mask the launch gathers: live_rows[0 .. n) = the rows r < live_T (<= MB_LIVE_MAX_ROWS) with live_mask[r] != 0, the first row b * live_L
+    // of EVERY sample (the [CLS] row the head reads: it carries a gradient whatever its mask word), and ALL rows of a sample (live_L
+    // rows each, at most MB_LIVE_MAX_SAMPLES samples) that has no set mask word, ascending; entries [n, count) name a row
+    // whose dY is zero -- the first dead row, else row live_T if live_T < live_Tp (the engine's zero pad rows) --; *live_count = count =
+    // max(192, n rounded up to 64).  No such row: every row is live and live_T == live_Tp is a multiple of 64, count = max(192, n) and the
+    // entries past n (n < 192 only) are never read by a launch that has K = live_Tp.  live_rows holds max(192, live_Tp) entries.  May be null
+    uint32_t* live_rows; uint32_t* live_count; const int64_t* live_mask; int live_T, live_Tp, live_L;
+    // cls_rows / cls_count (with live_rows; may be null): the rows b * live_L alone -- what the top layer's out-proj / ffn1 / ffn2 dY is
+    // non-zero on --, padded with the same zero row to max(192, B rounded up to 64); a batch without a zero row gets the rows 0 .. T-1.
+    // cls_rows holds as many entries as live_rows
+    uint32_t* cls_rows; uint32_t* cls_count;
     // MAG's weights packed into the operands of its regrouped GEMMs (mag_pack.h) by EXTRA blocks of this launch, which is waiting for
     // PCIe anyway: the first `copy_blocks` blocks (filled by step_prologue) do everything above, the rest this.  W_hv == null: none
     struct MagPackW { const float* W_hv; const float* W_ha; const float* W_v; const float* W_a; void* We; void* Wv; void* Wa; MagDims d; int dtype; } magw;

@@ -764,9 +764,85 @@ __device__ __forceinline__ uint64_t splitmix64_dev(uint64_t x) {
     return x ^ (x >> 31);
 }
 
+// The live-row list of the batch (PrologueArgs::live_rows), by one block: thread t owns the rows [t * S, (t + 1) * S), S = ceil(T / 256).
+// Every mask word is loaded ONCE (the mask may be pinned host memory: all of a thread's loads are in flight together, one round trip)
+// into a bitmap in LDS; then one block-wide exclusive scan of the 256 counts, and the rows go out in ascending order.  Live is
+//   * a row whose mask word is set;
+//   * row b * L of every sample, whatever its mask word: the head reads hidden[:, 0] and attention masks keys, never queries, so the
+//     [CLS] row carries a gradient in every layer (the out-proj / ffn dY and the Q third of dqkv);
+//   * every row of a sample without any set mask word: its softmax runs over all of its keys (attn_common.h common_key_bias).
+// cls_rows (may be null): the rows b * L, padded to max(192, B rounded up to 64) with the same zero row; without such a row (all live,
+// T == Tp) a copy of the live list.
+__device__ void live_rows_block(const PrologueArgs& a) {
+    __shared__ uint32_t cnt[256];
+    __shared__ uint32_t first_dead;
+    __shared__ uint32_t real[MB_LIVE_MAX_SAMPLES / 32];      // bit b: sample b has a set mask word
+    __shared__ uint32_t mbit[MB_LIVE_MAX_ROWS / 32];         // bit r: mask word r is set
+    const int t = threadIdx.x, T = a.live_T, L = a.live_L, S = (T + 255) / 256;
+    const int r0 = min(t * S, T), r1 = min(r0 + S, T);
+    if (t == 0) first_dead = 0xffffffffu;
+    for (int i = t; i < MB_LIVE_MAX_SAMPLES / 32; i += 256) real[i] = 0u;
+    for (int i = t; i < MB_LIVE_MAX_ROWS / 32; i += 256) mbit[i] = 0u;
+    __syncthreads();
+    for (int base = r0; base < r1; base += 16) {          // (16 loads issued before the first is looked at: S <= 16 up to T = 4,096)
+        int64_t w[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) w[k] = base + k < r1 ? __builtin_nontemporal_load(a.live_mask + base + k) : 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (w[k] != 0) {
+                const int r = base + k, b = r / L;
+                atomicOr(&real[b >> 5], 1u << (b & 31));
+                atomicOr(&mbit[r >> 5], 1u << (r & 31));
+            }
+    }
+    __syncthreads();
+    auto is_live = [&](int r) {
+        const int b = r / L;
+        return ((mbit[r >> 5] >> (r & 31)) & 1u) || r == b * L || !((real[b >> 5] >> (b & 31)) & 1u);
+    };
+    uint32_t n = 0, dead = 0xffffffffu;
+    for (int r = r0; r < r1; ++r) {
+        if (is_live(r)) ++n;
+        else if (dead == 0xffffffffu) dead = (uint32_t)r;
+    }
+    cnt[t] = n;
+    __syncthreads();
+    if (dead != 0xffffffffu) atomicMin(&first_dead, dead);
+    for (int d = 1; d < 256; d <<= 1) {          // inclusive Hillis-Steele scan
+        const uint32_t v = t >= d ? cnt[t - d] : 0u;
+        __syncthreads();
+        cnt[t] += v;
+        __syncthreads();
+    }
+    const uint32_t total = cnt[255];
+    uint32_t o = cnt[t] - n;
+    for (int r = r0; r < r1; ++r)
+        if (is_live(r)) a.live_rows[o++] = (uint32_t)r;
+    uint32_t pad = first_dead;
+    const bool have_pad = pad != 0xffffffffu || T < a.live_Tp;
+    if (pad == 0xffffffffu) pad = T < a.live_Tp ? (uint32_t)T : 0u;      // (0: all live and T == Tp -- entries no launch with K = Tp reads)
+    const uint32_t count = max(192u, (total + 63u) / 64u * 64u);
+    for (uint32_t i = total + t; i < count; i += 256) a.live_rows[i] = pad;
+    if (t == 0) *a.live_count = count;
+    if (a.cls_rows != nullptr) {
+        const uint32_t nb = (uint32_t)(T / L);
+        if (have_pad) {
+            const uint32_t cc = max(192u, (nb + 63u) / 64u * 64u);
+            for (uint32_t i = t; i < cc; i += 256) a.cls_rows[i] = i < nb ? i * (uint32_t)L : pad;
+            if (t == 0) *a.cls_count = cc;
+        } else {                                 // every row is live: rows 0 .. T-1 (the padding of a list shorter than 192 as above)
+            for (uint32_t i = t; i < count; i += 256) a.cls_rows[i] = i < total ? i : pad;
+            if (t == 0) *a.cls_count = count;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a) {
+    if (a.live_rows != nullptr && blockIdx.x == gridDim.x - 1) { live_rows_block(a); return; }      // (the launcher's one extra block)
     if ((int)blockIdx.x >= a.copy_blocks) {         // the extra blocks: MAG's weight operands (device memory only)
-        const size_t first = (size_t)(blockIdx.x - a.copy_blocks) * 256 + threadIdx.x, stride = (size_t)(gridDim.x - a.copy_blocks) * 256;
+        const size_t first = (size_t)(blockIdx.x - a.copy_blocks) * 256 + threadIdx.x,
+                     stride = (size_t)(gridDim.x - a.copy_blocks - (a.live_rows != nullptr ? 1 : 0)) * 256;
         const PrologueArgs::MagPackW& w = a.magw;
         if (w.dtype == DT_BF16) mag_pack_w_range<bf16>(w.W_hv, w.W_ha, w.W_v, w.W_a, (bf16*)w.We, (bf16*)w.Wv, (bf16*)w.Wa, w.d, first, stride);
         else mag_pack_w_range<float>(w.W_hv, w.W_ha, w.W_v, w.W_a, (float*)w.We, (float*)w.Wv, (float*)w.Wa, w.d, first, stride);
@@ -883,6 +959,12 @@ int step_prologue(const PrologueArgs& a, hipStream_t st) {
         if (!a.magw.W_ha || !a.magw.W_v || !a.magw.W_a || !a.magw.We || !a.magw.Wv || !a.magw.Wa) return MB_ERR_ARG;
         if (a.magw.dtype != DT_BF16 && a.magw.dtype != DT_F32) return MB_ERR_DTYPE;
         grid += 256;                                // one more block per CU, next to the ones that sit on their PCIe round trips
+    }
+    if (a.live_rows != nullptr) {
+        if (!a.live_count || !a.live_mask || a.live_T < 1 || a.live_Tp < a.live_T || a.live_L < 1 || a.live_T % a.live_L ||
+            a.live_T / a.live_L > MB_LIVE_MAX_SAMPLES || a.live_T > MB_LIVE_MAX_ROWS || (a.cls_rows && !a.cls_count))
+            return MB_ERR_ARG;
+        grid += 1;                                  // the LAST block builds the live-row list
     }
     hipLaunchKernelGGL(step_prologue_kernel, dim3(grid), dim3(256), 0, st, b);
     return (int)hipGetLastError();

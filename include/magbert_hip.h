@@ -93,6 +93,16 @@ int mb_debug_gemm_grouped_ex(int dtype, int count, const int* M, const int* N, i
                              size_t n4, int blocks, int zero_grad, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int step, int correct_bias, float grad_scale, void* adam_dev, void* stream);
 int mb_debug_gemm_last_kernel(char* out, int cap);
+/* mb_debug_gemm_grouped_rows: mb_gemm_grouped_wgrad with a gathered k loop (bf16, tile 256 only; else MB_ERR_MODE): problem g sums over the
+ *   rows rows[g][0 .. n) of dY_g and X_g in list order, n = min(K, *nrows[g]) -- a multiple of 64, at least 192; rows[g] (device, 32-byte
+ *   aligned uint32) holds at least that many entries < K.  rows[g] == NULL: all K rows.  overwrite as mb_debug_gemm_grouped_ex.
+ * mb_debug_live_rows: the step prologue's lists of a [B][L] int64 mask (device): live_rows (max(192, Tp) uint32) and *live_count; cls_rows /
+ *   cls_count (both or neither; may be NULL): the [CLS]-row list, same capacity. */
+int mb_debug_gemm_grouped_rows(int dtype, int count, const int* M, const int* N, int K, const void* const* dY, const int* ldy,
+                               const void* const* X, const int* ldx, float* const* dW, const int* ldw, const int* overwrite, int tile,
+                               const void* const* rows, const void* const* nrows, void* stream);
+int mb_debug_live_rows(const int64_t* mask, int B, int L, int Tp, void* live_rows, void* live_count, void* cls_rows, void* cls_count,
+                       void* stream);
 
 /* `count` (<= 4) weight gradients dW_g[M_g][N_g] += dY_g[K][M_g]^T X_g[K][N_g] in ONE launch (fp32 accumulate) -- the
  * four torch.nn.Linear weight gradients autograd produces per BertLayer (mm_backward under loss.backward(),
@@ -250,6 +260,12 @@ const float* mb_bert_pooled_output(const mb_bert_engine* e);    /* [B][H] fp32 (
  * mb_xlnet_hidden_state, whose list holds the tensor in front of the gate because its reference collects it there.  set_attention_output: the next forwards also write every layer's attention probabilities AFTER
  * dropout (what BertSelfAttention returns with output_attentions) to probs [num_layers][B][nh][L][L] fp32; NULL turns it off. */
 const void* mb_bert_hidden_state(const mb_bert_engine* e, int i);
+/* test hook: the operands the last backward multiplied for layer `layer`'s weight gradients: which = 0 ffn2, 1 ffn1, 2 out-proj, 3 qkv -> dY,
+ * which + 4 -> X (the saved forward activation); *ld = the row pitch in elements.  The dY buffers alternate between even and odd layers:
+ * only those of the two layers the backward ran last are still there. */
+const void* mb_bert_debug_wgrad_dy(const mb_bert_engine* e, int layer, int which, int* ld);
+/* test hook: the weight-gradient launches of the last single-call step that summed over a row list (0: all dense) */
+int mb_bert_debug_live_wgrad_launches(const mb_bert_engine* e);
 int mb_bert_set_attention_output(mb_bert_engine* e, float* probs);
 /* Optional INPUTS of MAG_BertModel.forward (bert.py:160, 185-209).  Both are sticky until reset with NULL, apply to
  * mb_bert_forward / mb_bert_backward only (mb_bert_train_step returns MB_ERR_MODE while one is set), and point at caller-owned

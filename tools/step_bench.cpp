@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
     double layer_decay = 1.0, head_lr_mult = 1.0, max_grad_norm = 0.0;
     int freeze_layers = 0, freeze_emb = 0, act = MB_ACT_GELU, inject = -1;      // --inject N: MAG in front of layer N (default: 0 | MAG-XLNet: 1)
+    int all_live = 0;           // --all_live 1: every sample has L - 2 words (no padding token: the worst case of the live-row weight gradients)
     const char* act_name = "gelu";
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
@@ -67,6 +68,7 @@ int main(int argc, char** argv) {
         else if (k == "--max_grad_norm") max_grad_norm = atof(v);
         else if (k == "--freeze_layers") freeze_layers = atoi(v); else if (k == "--freeze_emb") freeze_emb = atoi(v);
         else if (k == "--inject") inject = atoi(v);
+        else if (k == "--all_live") all_live = atoi(v);
         else if (k == "--act") {
             const char* names[] = {"gelu", "relu", "swish", "gelu_new", "mish"};
             act = strcmp(v, "silu") == 0 ? MB_ACT_SWISH : -1;
@@ -76,7 +78,7 @@ int main(int argc, char** argv) {
         }
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --inject)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --inject --all_live)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -138,7 +140,8 @@ int main(int argc, char** argv) {
         Batch b = view(hb[k]);
         memset(hb[k], 0, bytes);
         for (int s = 0; s < B; ++s) {
-            const int nw = 5 + (int)(rnd() % (uint64_t)(L - 2 - 5 + 1));
+            const int nw_drawn = 5 + (int)(rnd() % (uint64_t)(L - 2 - 5 + 1));      // (drawn either way: the same ids and modalities follow)
+            const int nw = all_live ? L - 2 : nw_drawn;
             b.ids[s * L] = 101; b.mask[s * L] = 1;
             for (int t = 1; t <= nw; ++t) {
                 b.ids[s * L + t] = 1000 + (int64_t)(rnd() % 29522); b.mask[s * L + t] = 1;
