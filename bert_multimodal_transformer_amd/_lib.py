@@ -85,6 +85,12 @@ PROTOTYPES = {
     "mb_attention_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp]),
     "mb_attention_resident_forward": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp, _vp]),
     "mb_attention_resident_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),
+    "mb_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _i, _f, _vp, _vp]),
+    "mb_head_backward": (_i, [_i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _dk, _i, _f, _vp, _vp]),
+    "mb_bert_set_head_loss": (_i, [_vp, _i, _f, _vp]),
+    "mb_bert_get_head_loss": (_i, [_vp, C.POINTER(_i), C.POINTER(_f), _vp, C.POINTER(_i)]),
+    "mb_xlnet_set_head_loss": (_i, [_vp, _i, _f, _vp]),
+    "mb_xlnet_get_head_loss": (_i, [_vp, C.POINTER(_i), C.POINTER(_f), _vp, C.POINTER(_i)]),
     "mb_attention_tiled_stats_bytes": (_sz, [_i, _i, _i]),
     "mb_attention_tiled_forward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp, _vp]),
     "mb_attention_tiled_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),

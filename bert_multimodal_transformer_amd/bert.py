@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import losses as _losses
 from .global_configs import ACOUSTIC_DIM, VISUAL_DIM
 
 
@@ -211,6 +212,7 @@ class _Core(object):
         self.training_last = False
         self._own_stream = None
         self.stage_hooks = []          # callables hook(stage) run after each backward stage (DataParallel)
+        self.loss = _losses.HeadLoss()         # the head's objective (set_loss); every engine this core creates gets it
         self._make_engine(1, 8)
         n = self._fn("param_count")(self.handle)
         self.n_params = n
@@ -265,6 +267,22 @@ class _Core(object):
         self._optional = (None, None, None, None, None)    # a new engine starts without head_mask / inputs_embeds / position_ids / perm_mask
         self._update_map = None                            # ... and without a segment map of update classes (train_step)
         self.max_B, self.max_L = B, L
+        self._apply_loss()                                 # ... but with this model's objective
+
+    def _apply_loss(self):
+        vec = self.loss.vector
+        arr = None if vec is None else (C.c_float * len(vec))(*vec)
+        _lib.check(self._fn("set_head_loss")(self.handle, self.loss.code, float(self.loss.beta or 0.0), arr))
+
+    def set_loss(self, loss):
+        """a checked losses.HeadLoss -> this core and its engine (include/magbert_hip.h: mb_*_set_head_loss; sticky, between steps)"""
+        old, self.loss = self.loss, loss
+        try:
+            self._apply_loss()
+        except Exception:
+            self.loss = old
+            raise
+        self._lab_ptr = None        # labels staged for the old objective may have another count: a backward needs a new forward
 
     def _comm_join(self):
         """sharded optimizer update under data parallel (distributed.Comm.set_sharding): the operands of this pass come back from the
@@ -385,15 +403,8 @@ class _Core(object):
         B, L = input_ids.shape
         dev = self.device
         lab_in = None if labels is None else labels.reshape(-1)
-        nl = int(self.config.num_labels)
-        if lab_in is not None and lab_in.numel() != B * (1 if nl > 1 else nl):
-            raise ValueError("labels: expected %d values for a batch of %d, got %d" % (B, B, lab_in.numel()))
-        if lab_in is not None and nl > 1:
-            # fused cross entropy (head.hip): class indices travel as fp32; what torch's CrossEntropyLoss would reject or treat
-            # specially must not silently become class 0 (ignore_index = -100 is not built)
-            lf = lab_in.detach().float()
-            if bool(((lf != lf.round()) | (lf < 0) | (lf >= nl)).any()):
-                raise ValueError("labels of the fused cross entropy must be class indices in [0, %d) (ignore_index is not supported)" % nl)
+        if lab_in is not None:      # count and values per kind (losses.check_labels): B * num_labels targets, or B targets / class indices
+            _losses.check_labels(self.loss, lab_in, B, int(self.config.num_labels))
         six = (input_ids, visual, acoustic, attention_mask, token_type_ids, lab_in)
         if self._pinned_batch(six, B, L):
             ptrs = [None if t is None else C.c_void_p(t.data_ptr()) for t in six]
@@ -1032,11 +1043,17 @@ class _MagBertBase(nn.Module):
         multimodal_config = kwargs.pop("multimodal_config", model_args[0] if model_args else None)
         num_labels = kwargs.pop("num_labels", 1)
         want_info = kwargs.pop("output_loading_info", False)
+        # the head's objective: set_loss's arguments as keywords (loss="l1", beta=..., pos_weight=..., weight=...)
+        loss_kw = {k: kwargs.pop(k) for k in ("loss", "beta", "pos_weight", "weight") if k in kwargs}
         # no config given: the `config.json` next to the checkpoint says which model it is (a bert-large directory loads as
         # bert-large); without one it is bert-base-uncased, as before
         config = config or cls._config_beside(pretrained_model_name_or_path, num_labels) or cls._default_config(num_labels)
         config.num_labels = num_labels
         model = cls(config, multimodal_config, **kwargs)
+        if loss_kw:
+            if not hasattr(model, "set_loss"):
+                raise ValueError("%s has no head: loss / beta / pos_weight / weight belong to the *ForSequenceClassification classes" % cls.__name__)
+            model.set_loss(loss_kw.pop("loss", "default"), **loss_kw)
         path = _pretrained_file(pretrained_model_name_or_path, cls.__name__)
         sd = torch.load(path, map_location="cpu")
         model.loading_info = load_pretrained_state_dict(model, sd, cls.base_model_prefix, source=path)
@@ -1059,8 +1076,23 @@ class _FusedStep(object):
     """Fused training surface shared by MAG_BertForSequenceClassification and MAG_XLNetForSequenceClassification
     (what the bundled driver's train_epoch and bench.py call instead of the reference's five-line step)."""
 
+    def set_loss(self, name, beta=None, pos_weight=None, weight=None):
+        """The objective of every pass that is given labels -- training_step, train_step and its graph, stage_step, eval_step, the
+        data-parallel steps, and forward(labels=...) on the autograd route: "default" (MSE at num_labels == 1, else cross entropy: the
+        reference's classes), "mse", "l1", "smooth_l1" (beta, default 1.0; 0 is l1), "bce" (pos_weight: num_labels values or None) and
+        "cross_entropy" (weight: num_labels class weights or None; num_labels >= 2) -- torch.nn.functional's functions of those names
+        under mean reduction.  mse / l1 / smooth_l1 / bce take label_ids of shape [B, num_labels], the others [B].  Sticky, legal
+        between steps; an unknown name or an argument that does not belong to the kind raises ValueError."""
+        self._core.set_loss(_losses.make_loss(name, int(self.config.num_labels), beta=beta, pos_weight=pos_weight, weight=weight))
+
+    @property
+    def loss(self):
+        """what set_loss installed (losses.HeadLoss: name, beta, pos_weight, weight)"""
+        return self._core.loss
+
     def training_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, loss_scale=1.0):
-        """forward + loss + backward in two C calls, no host sync.  The loss is the one the reference's forward computes when it is
+        """forward + loss + backward in two C calls, no host sync.  The loss is the one set_loss installed; by default the one the
+        reference's forward computes when it is
         given labels (bert.py:313-322 / xlnet.py:515-524): MSE for num_labels == 1 (what the driver trains, multimodal_driver.py:372-373),
         cross entropy over the class indices in label_ids otherwise.
         Returns the device scalar holding this step's loss (running sum is in .loss_running())."""
@@ -1323,10 +1355,7 @@ class MAG_BertForSequenceClassification(_FusedStep, _MagBertBase):
             outputs = outputs + (core.hidden_states(B, L),)
         if output_attentions:
             outputs = outputs + (tuple(probs[l] for l in range(core.n_layers)),)
-        if labels is not None:                                        # bert.py:313-322
-            if self.num_labels == 1:
-                loss = torch.nn.functional.mse_loss(logits.view(-1), labels.to(logits.device).float().view(-1))
-            else:
-                loss = torch.nn.functional.cross_entropy(logits.view(-1, self.num_labels), labels.to(logits.device).view(-1))
+        if labels is not None:                                        # bert.py:313-322, or what set_loss installed
+            loss = _losses.torch_loss(core.loss, logits, labels, self.num_labels)
             outputs = (loss,) + outputs
         return outputs

@@ -477,6 +477,22 @@ static int resident_check(int dtype, int B, int L, int nh, const DropKey& drop) 
     if (dtype != DT_BF16 && dtype != DT_F32) return MB_ERR_DTYPE;
     return MB_OK;
 }
+// the head's two kernels as the engines launch them (every pointer a device pointer)
+int mb_head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits, float* loss,
+                    float* loss_run, int B, int H, int num_labels, const mb_dropkey* drop, int loss_kind, float loss_param,
+                    const float* loss_vec, void* stream) {
+    if (!z || !Wc || !bc || !pooled || !logits || B < 0 || num_labels < 1) return MB_ERR_ARG;
+    return head_forward(z, Wc, bc, labels, pooled, logits, loss, loss_run, B, H, num_labels, dk(drop), (hipStream_t)stream,
+                        HeadLoss{loss_kind, loss_param, loss_vec});
+}
+int mb_head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale, const float* pooled,
+                     const float* Wc, void* dz, float* dWc, float* dbc, float* dbp, void* zero_p, size_t zero_bytes, int B, int H,
+                     int num_labels, const mb_dropkey* drop, int loss_kind, float loss_param, const float* loss_vec, void* stream) {
+    if (!pooled || !Wc || !dz || B < 0 || num_labels < 1) return MB_ERR_ARG;
+    return head_backward(dtype, dlogits, logits, labels, loss_scale, pooled, Wc, dz, dWc, dbc, B, H, num_labels, dk(drop),
+                         (hipStream_t)stream, GradAcc{}, dbp, zero_p, zero_bytes, HeadLoss{loss_kind, loss_param, loss_vec});
+}
+
 int mb_attention_resident_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
                                   const mb_dropkey* drop, const float* head_scale, float* probs, void* stream) {
     if (int e = resident_check(dtype, B, L, nh, dk(drop))) return e;
@@ -585,6 +601,7 @@ void mb_bert_destroy(mb_bert_engine* e) {
     e->drop_graphs();
     e->free_class_table();
     e->free_clip_buf();
+    e->free_head_loss();
     delete e;
 }
 int mb_bert_num_tensors(const mb_bert_engine* e) { return (int)e->tensors.size(); }
@@ -702,8 +719,9 @@ static int bert_forward_range(mb_bert_engine* e, const int64_t* input_ids, const
     CK(gemm(dt, GEMM_NT, EPI_BIAS_F32, B, H, H, ws + e->ws_x[c.num_layers], L * H, e->W(e->wp), H, nullptr, H, nullptr, z,
             P + e->bp, nullptr, 0, kNoDrop, 1, 64, st));
     if (loss && !(e->in_step && e->loss_cleared)) CK(zero_fill(loss, 4, st));
+    if (labels && !e->in_step) CK(e->sync_head_loss());          // (a step did this before its prologue, outside the capture)
     CK(head_forward(z, P + e->wc, P + e->bc, labels, (float*)(ws + e->ws_head_pooled), logits, loss, loss_run, B, H,
-                    c.num_labels, e->key(SITE_HEAD, c.hidden_dropout), st));
+                    c.num_labels, e->key(SITE_HEAD, c.hidden_dropout), st, e->head_loss()));
     return MB_OK;
 }
 
@@ -766,9 +784,10 @@ int mb_bert_backward(mb_bert_engine* e, const float* dlogits, const float* label
             // ---- head + pooler
             // (one launch: dz, the classifier gradients, the pooler bias gradient = column sums of dz, and the clearing of the token
             //  gradient buffer whose [CLS] rows the dgrad below fills)
+            if (labels && !e->in_step) CK(e->sync_head_loss());
             CK(head_backward(dt, dlogits, e->logits, labels, loss_scale, (const float*)(ws + e->ws_head_pooled), P + e->wc,
                              ws + e->ws_dz, G + e->wc, G + e->bc, B, H, c.num_labels, e->key(SITE_HEAD, c.hidden_dropout),
-                             st, acc, G + e->bp, ws + e->ws_dxa, (size_t)T * H * esize(dt)));
+                             st, acc, G + e->bp, ws + e->ws_dxa, (size_t)T * H * esize(dt), e->head_loss()));
             const char* xf = ws + e->ws_x[NL];
             CK(gemm(dt, GEMM_TN, EPI_ACCUM_F32, H, H, B, ws + e->ws_dz, H, xf, L * H, nullptr, H, nullptr, G + e->wp, nullptr,
                     nullptr, 0, kNoDrop, 1, 64, st));
@@ -1154,6 +1173,7 @@ int mb_bert_stage_forward(mb_bert_engine* e, const int64_t* input_ids, const flo
     char* ws = e->ws;
     e->training = 1;
     CK(prepare_pass(e, B * L, st));
+    CK(e->sync_head_loss());
     PrologueArgs pa = {};
     e->fill_copies(pa, ws, input_ids, visual, acoustic, attention_mask, token_type_ids, labels, B, L, c.visual_dim, c.acoustic_dim, c.num_labels);
     pa.seed = seed; pa.step = step; pa.keys = e->key_state(ws); pa.nsites = e->nsites;
@@ -1271,6 +1291,14 @@ int mb_bert_set_head_mask(mb_bert_engine* e, const float* head_mask) {
     if (!e) return MB_ERR_ARG;
     e->head_mask = head_mask;
     return MB_OK;
+}
+int mb_bert_set_head_loss(mb_bert_engine* e, int kind, float param, const float* vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_head_loss(kind, param, vec, e->c.num_labels);
+}
+int mb_bert_get_head_loss(const mb_bert_engine* e, int* kind, float* param, float* vec, int* has_vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->get_head_loss(kind, param, vec, has_vec);
 }
 int mb_bert_set_inputs_embeds(mb_bert_engine* e, const float* inputs_embeds) {
     if (!e) return MB_ERR_ARG;

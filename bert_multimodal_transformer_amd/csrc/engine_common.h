@@ -736,9 +736,66 @@ struct StepMixin {
         } else {
             cp(vis, ws_in_vis, T * V * 4); cp(aco, ws_in_aco, T * A * 4);
         }
-        (void)num_labels;          // one float per sample either way: the regression target (num_labels == 1) or the class index
-        if (lab) cp(lab, ws_in_lab, (size_t)B * 4);
+        // one float per sample -- the regression target (num_labels == 1) or the class index -- or, under a per-element loss, one per logit
+        if (lab) cp(lab, ws_in_lab, label_floats(B, num_labels) * 4);
     }
+    // The head's objective (kernels.h HeadLoss; include/magbert_hip.h: mb_*_set_head_loss).  Sticky, legal between steps, checked before
+    // any device call.  kind and scalar are kernel arguments, baked into every captured graph that holds a head launch: a change drops the
+    // engine's graphs (the next step captures again).  The vector lives in device memory of the engine's own, like class_table -- never
+    // the workspace -- and is uploaded by the first pass after the setter, outside any capture (sync_head_loss).
+    int loss_kind = HL_DEFAULT; float loss_param = 0.f;
+    std::vector<float> loss_vec;             // host copy (empty = none)
+    float* loss_vec_dev = nullptr; size_t loss_vec_cap = 0; bool loss_vec_dirty = false;
+    size_t label_floats(int B, int num_labels) const { return (size_t)B * (head_loss_per_element(loss_kind) ? num_labels : 1); }
+    HeadLoss head_loss() const { return HeadLoss{loss_kind, loss_param, loss_vec.empty() ? nullptr : loss_vec_dev}; }
+    int set_head_loss(int kind, float param, const float* vec, int num_labels) {
+        if (kind < HL_DEFAULT || kind > HL_CE) return MB_ERR_ARG;
+        if (kind == HL_CE && num_labels < 2) return MB_ERR_ARG;
+        if (kind == HL_SMOOTH_L1 && !(std::isfinite(param) && param >= 0.f)) return MB_ERR_ARG;
+        const bool takes_vec = kind == HL_BCE || kind == HL_CE;
+        if (vec && !takes_vec) return MB_ERR_ARG;
+        if (vec) {
+            bool any = false;
+            for (int k = 0; k < num_labels; ++k) {
+                if (!(std::isfinite(vec[k]) && vec[k] >= 0.f)) return MB_ERR_ARG;
+                any = any || vec[k] > 0.f;
+            }
+            if (!any) return MB_ERR_ARG;
+        }
+        if (kind != HL_SMOOTH_L1) param = 0.f;
+        std::vector<float> nv;
+        if (vec) nv.assign(vec, vec + num_labels);
+        if (kind == loss_kind && param == loss_param && nv == loss_vec) return MB_OK;
+        // graphs in flight read the old arguments (and the old vector): wait for them before they go
+        if (!graphs.empty() || !stage_graphs.empty()) { CK((int)hipDeviceSynchronize()); drop_graphs(); }
+        loss_kind = kind; loss_param = param;
+        loss_vec_dirty = loss_vec_dirty || nv != loss_vec;
+        loss_vec.swap(nv);
+        return MB_OK;
+    }
+    int get_head_loss(int* kind, float* param, float* vec, int* has_vec) const {
+        if (kind) *kind = loss_kind;
+        if (param) *param = loss_param;
+        if (has_vec) *has_vec = loss_vec.empty() ? 0 : 1;
+        if (vec) std::copy(loss_vec.begin(), loss_vec.end(), vec);
+        return MB_OK;
+    }
+    // the vector on the device before a head launch reads it (never inside a capture: the passes call it before they enqueue)
+    int sync_head_loss() {
+        if (!loss_vec_dirty || capturing) return MB_OK;
+        if (!loss_vec.empty()) {
+            if (loss_vec_cap < loss_vec.size()) {
+                if (loss_vec_dev) { CK((int)hipDeviceSynchronize()); hipFree(loss_vec_dev); loss_vec_dev = nullptr; loss_vec_cap = 0; }
+                CK((int)hipMalloc((void**)&loss_vec_dev, loss_vec.size() * sizeof(float)));
+                loss_vec_cap = loss_vec.size();
+            }
+            CK((int)hipDeviceSynchronize());            // launches already enqueued, on whichever stream, read the old values
+            CK((int)hipMemcpy(loss_vec_dev, loss_vec.data(), loss_vec.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        loss_vec_dirty = false;
+        return MB_OK;
+    }
+    void free_head_loss() { if (loss_vec_dev) { hipFree(loss_vec_dev); loss_vec_dev = nullptr; loss_vec_cap = 0; } }
     void staged(char* ws, bool with_labels, const void** six) const {
         six[0] = ws + ws_in_ids; six[1] = ws + ws_in_vis; six[2] = ws + ws_in_aco; six[3] = ws + ws_in_mask; six[4] = ws + ws_in_seg;
         six[5] = with_labels ? ws + ws_in_lab : nullptr;
@@ -765,6 +822,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     e->frz_elems = 0; e->frz_wgrad_skipped = e->frz_embed_skipped = 0;
     if (e->any_frozen && e->frz_dirty) CK(e->clear_frozen(e->G, st));
     if (m && e->n_classes > 0) CK(e->ensure_class_table());
+    CK(e->sync_head_loss());
     const bool clip = m && e->clip_max > 0.f;
     if (clip && variant > 0) return MB_ERR_MODE;          // (the data-parallel steps refuse before they get here)
     if (clip) CK(e->ensure_clip_buf(e->n_update_end()));

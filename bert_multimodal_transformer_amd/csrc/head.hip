@@ -4,19 +4,75 @@
 //   loss = mean((logits - labels)^2)                                  num_labels == 1 (the driver's regression)
 //   loss = mean_b(logsumexp(logits_b) - logits_b[label_b])            num_labels  > 1 (bert.py:318-320 / xlnet.py:519-522:
 //          CrossEntropyLoss; labels[b] then holds the class index of sample b as a float)
+// Other objectives (kernels.h HeadLoss, include/magbert_hip.h mb_*_set_head_loss): the kind is a kernel argument, uniform for the
+// launch -- a scalar branch, as EPI_BIAS_ACT switches its activation.  The per-element kinds read labels[b * nl + k]:
+//   mse        mean (x - y)^2                                         l1   mean |x - y|   (gradient 0 at x == y)
+//   smooth_l1  mean of 0.5 d^2 / beta where |d| < beta, else |d| - 0.5 beta   (beta == 0: the expressions of l1)
+//   bce        mean of (1 - y) x + (1 + (p_k - 1) y) (max(-x, 0) + log1p(exp(-|x|)))   p = pos_weight [nl] or null
+//   weighted cross entropy   sum_b w[y_b] nll_b / sum_b w[y_b]: every wave sums w[y_b] over the batch itself, in a fixed order
+//              (lane-strided, then wave_sum), so every block holds the same bits without a launch or an atomic of its own
+// The default kind -- MSE at num_labels == 1, the cross entropy without weights otherwise -- is an instantiation of its own (DEF), with
+// the expressions the kernels always had; `mse` at one label and the unweighted `cross_entropy` go through the same expressions.
 // One wave per sample; H = 256 * CH (CH chunks of 4 columns per lane: CH = 3 is bert-base, 4 bert-large).  Tiny, launch-latency bound.
 #include <algorithm>
 #include "kernels.h"
 
 namespace mb {
 
+__device__ __forceinline__ float head_sign(float d) { return (float)(d > 0.f) - (float)(d < 0.f); }      // sign(0) = 0
+// loss of one logit x against its target y under a per-element kind (class k: bce's pos_weight entry)
+__device__ __forceinline__ float head_loss_term(const HeadLoss hl, float x, float y, int k) {
+    const float d = x - y;
+    switch (hl.kind) {
+        case HL_MSE: return d * d;
+        case HL_L1: return fabsf(d);
+        case HL_SMOOTH_L1: {
+            const float ad = fabsf(d);
+            return ad < hl.param ? 0.5f * d * d / hl.param : ad - 0.5f * hl.param;
+        }
+        default: {      // HL_BCE
+            const float lw = hl.vec ? 1.0f + (hl.vec[k] - 1.0f) * y : 1.0f;
+            return (1.0f - y) * x + lw * (fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x))));
+        }
+    }
+}
+// ... and its derivative in x (before the division by B * nl)
+__device__ __forceinline__ float head_loss_grad(const HeadLoss hl, float x, float y, int k) {
+    const float d = x - y;
+    switch (hl.kind) {
+        case HL_MSE: return 2.0f * d;
+        case HL_L1: return head_sign(d);
+        case HL_SMOOTH_L1: return fabsf(d) < hl.param ? d / hl.param : head_sign(d);
+        default: {      // HL_BCE: sigmoid(-x) from exp(-|x|), so neither tail overflows
+            const float lw = hl.vec ? 1.0f + (hl.vec[k] - 1.0f) * y : 1.0f;
+            const float e = expf(-fabsf(x));
+            const float sg = (x >= 0.f ? e : 1.0f) / (1.0f + e);
+            return (1.0f - y) - lw * sg;
+        }
+    }
+}
+// weighted cross entropy: w[class], 0 for an index outside the table (the hosts refuse such labels; nothing is read out of bounds)
+__device__ __forceinline__ float head_class_weight(const float* __restrict__ w, int y, int nl) {
+    return (unsigned)y < (unsigned)nl ? w[y] : 0.f;
+}
+// ... and the summed weights of the batch's targets: the same bits in every wave of every block (whole waves call this)
+__device__ __forceinline__ float head_weight_sum(const float* __restrict__ labels, const float* __restrict__ w, int B, int nl, int lane) {
+    float t = 0.f;
+    for (int i = lane; i < B; i += 64) t += head_class_weight(w, (int)labels[i], nl);
+    return wave_sum(t);
+}
+
 // Atomics on ONE address serialise at the L2 (measured: 48 samples x 2 atomics = most of a 15 us launch), so the four waves of
 // a block meet in LDS first: one loss atomic per block, one classifier-gradient atomic per column per block.
-template <int CH>
+// DEF: the default kind as an instantiation of its own -- MSE at nl == 1, cross entropy otherwise, written with the expressions and
+// the label indexing the kernels had before there was a choice, so that the step every untouched model runs compiles to what it was
+// (the general form costs the forward 11 to 22 VGPRs and measured +0.2 % on the MAG-BERT step: profiles/head_loss.txt).
+template <int CH, bool DEF>
 __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__ z, const float* __restrict__ Wc,
                                                        const float* __restrict__ bc, const float* __restrict__ labels,
                                                        float* __restrict__ pooled, float* __restrict__ logits, float* loss,
-                                                       float* loss_run, int B, int nl, DropKey drop) {
+                                                       float* loss_run, int B, int nl, DropKey drop, HeadLoss hl_) {
+    const HeadLoss hl = DEF ? HeadLoss{HL_MSE, 0.f, nullptr} : hl_;       // (DEF: what the per-element branch runs; `ce` picks the branch)
     drop.resolve();
     constexpr int H = CH * 256;
     __shared__ float lsum[4];
@@ -39,7 +95,10 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__
         }
         // cross entropy (nl > 1): online log-sum-exp over the classes, kept by lane 0
         float mx = -3.0e38f, se = 0.f, tgt = 0.f;
-        const int y = (labels && nl > 1) ? (int)labels[b] : -1;
+        const bool ce = DEF ? nl > 1 : hl.kind == HL_CE;               // uniform
+        const int y = (labels && ce) ? (int)labels[b] : -1;
+        const float fN = DEF ? (float)B : (float)(B * nl);             // per-element kinds: the mean runs over B * nl
+        const float wtot = (labels && ce && hl.vec) ? head_weight_sum(labels, hl.vec, B, nl, lane) : 0.f;
         for (int k = 0; k < nl; ++k) {
             float s = 0.f;
 #pragma unroll
@@ -51,9 +110,8 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__
             s = wave_sum(s) + bc[k];
             if (lane == 0) {
                 logits[(size_t)b * nl + k] = s;
-                if (labels && nl == 1) {
-                    const float d = s - labels[b];
-                    mine += d * d / (float)B;
+                if (labels && !ce) {
+                    mine += head_loss_term(hl, s, DEF ? labels[b] : labels[(size_t)b * nl + k], k) / fN;
                 } else if (labels) {
                     const float nm = fmaxf(mx, s);
                     se = se * __expf(mx - nm) + __expf(s - nm);
@@ -62,7 +120,10 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__
                 }
             }
         }
-        if (lane == 0 && labels && nl > 1) mine = (mx + __logf(se) - tgt) / (float)B;
+        if (lane == 0 && labels && ce) {
+            if (hl.vec) mine = head_class_weight(hl.vec, y, nl) * (mx + __logf(se) - tgt) / wtot;
+            else mine = (mx + __logf(se) - tgt) / (float)B;
+        }
     }
     if (labels == nullptr || (loss == nullptr && loss_run == nullptr)) return;      // uniform
     if (lane == 0) lsum[wave] = mine;
@@ -74,13 +135,14 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const float* __restrict__
     }
 }
 
-template <class T, int CH>
+template <class T, int CH, bool DEF>
 __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ logits,
                                                        const float* __restrict__ labels, float loss_scale,
                                                        const float* __restrict__ pooled, const float* __restrict__ Wc,
                                                        T* __restrict__ dz, float* dWc, float* dbc, int B, int nl,
                                                        DropKey drop, GradAcc acc, float* dbp, u32x4* __restrict__ zero_p,
-                                                       size_t zero_n16, int nb) {
+                                                       size_t zero_n16, int nb, HeadLoss hl_) {
+    const HeadLoss hl = DEF ? HeadLoss{HL_MSE, 0.f, nullptr} : hl_;
     // blocks [nb, gridDim.x): clear zero_p[0, zero_n16) -- the token-gradient buffer whose [CLS] / last-token rows the next launch
     // fills (one launch less per backward than a separate zero_fill)
     if ((int)blockIdx.x >= nb) {
@@ -108,19 +170,25 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__
     }
     float lse = 0.f;
     int y = -1;
-    if (valid && !dlogits && nl > 1) {          // cross entropy: d logit_k = (softmax_k - [k == label]) / B
+    const bool ce = DEF ? nl > 1 : hl.kind == HL_CE;           // uniform
+    const float fN = DEF ? (float)B : (float)(B * nl);
+    float wy = 1.0f, wtot = 0.f;                // weighted cross entropy: this sample's class weight, the batch's summed weights
+    if (!dlogits && ce && hl.vec) wtot = head_weight_sum(labels, hl.vec, B, nl, lane);
+    if (valid && !dlogits && ce) {              // cross entropy: d logit_k = (softmax_k - [k == label]) / B
         float mx = -3.0e38f;
         for (int k = 0; k < nl; ++k) mx = fmaxf(mx, logits[(size_t)b * nl + k]);
         float se = 0.f;
         for (int k = 0; k < nl; ++k) se += __expf(logits[(size_t)b * nl + k] - mx);
         lse = mx + __logf(se);
         y = (int)labels[b];
+        if (hl.vec) wy = head_class_weight(hl.vec, y, nl);
     }
     for (int k = 0; k < nl; ++k) {
         float dl = 0.f;
         if (valid) {
             if (dlogits) dl = dlogits[(size_t)b * nl + k];
-            else if (nl == 1) dl = 2.0f * (logits[b] - labels[b]) / (float)B * loss_scale;
+            else if (!ce) dl = (DEF ? head_loss_grad(hl, logits[b], labels[b], k) : head_loss_grad(hl, logits[(size_t)b * nl + k], labels[(size_t)b * nl + k], k)) / fN * loss_scale;
+            else if (hl.vec) dl = wy * (__expf(logits[(size_t)b * nl + k] - lse) - (k == y ? 1.0f : 0.0f)) / wtot * loss_scale;
             else dl = (__expf(logits[(size_t)b * nl + k] - lse) - (k == y ? 1.0f : 0.0f)) / (float)B * loss_scale;
         }
 #pragma unroll
@@ -153,34 +221,47 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__
     }
 }
 
+// what the kernels take: a known kind, and no vector where the kind reads none (the default kind runs the DEF instantiation)
+static int head_loss_resolve(HeadLoss& hl, int nl) {
+    if (hl.kind < HL_DEFAULT || hl.kind > HL_CE || (hl.kind == HL_CE && nl < 2)) return MB_ERR_ARG;
+    if (hl.kind != HL_BCE && hl.kind != HL_CE) hl.vec = nullptr;
+    return MB_OK;
+}
+
 int head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits,
-                 float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st) {
+                 float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st, HeadLoss hl) {
     if (H != 256 && H != 512 && H != 768 && H != 1024) return MB_ERR_SHAPE;
     if (B <= 0) return MB_OK;
-#define MB_HEAD_FWD(CH) hipLaunchKernelGGL((head_fwd_kernel<CH>), dim3((B + 3) / 4), dim3(256), 0, st, z, Wc, bc, labels, pooled, logits, loss, \
-                                           loss_run, B, nl, drop)
+    if (int r = head_loss_resolve(hl, nl)) return r;
+#define MB_HEAD_FWD_(CH, DEF) hipLaunchKernelGGL((head_fwd_kernel<CH, DEF>), dim3((B + 3) / 4), dim3(256), 0, st, z, Wc, bc, labels, pooled, logits, loss, \
+                                                 loss_run, B, nl, drop, hl)
+#define MB_HEAD_FWD(CH) do { if (hl.kind == HL_DEFAULT) MB_HEAD_FWD_(CH, true); else MB_HEAD_FWD_(CH, false); } while (0)
     switch (H / 256) { case 1: MB_HEAD_FWD(1); break; case 2: MB_HEAD_FWD(2); break; case 3: MB_HEAD_FWD(3); break; default: MB_HEAD_FWD(4); break; }
 #undef MB_HEAD_FWD
+#undef MB_HEAD_FWD_
     return (int)hipGetLastError();
 }
 
 int head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale,
                   const float* pooled, const float* Wc, void* dz, float* dWc, float* dbc, int B, int H, int nl,
-                  DropKey drop, hipStream_t st, GradAcc acc, float* dbp, void* zero_p, size_t zero_bytes) {
+                  DropKey drop, hipStream_t st, GradAcc acc, float* dbp, void* zero_p, size_t zero_bytes, HeadLoss hl) {
     if (H != 256 && H != 512 && H != 768 && H != 1024) return MB_ERR_SHAPE;
     if (B <= 0) return MB_OK;
+    if (int r = head_loss_resolve(hl, nl)) return r;
     if (!dlogits && !(logits && labels)) return MB_ERR_ARG;
     if (zero_bytes % 16 || ((uintptr_t)zero_p & 15)) return MB_ERR_SHAPE;
     const int nb = (B + 3) / 4;
     const size_t n16 = zero_p ? zero_bytes / 16 : 0;
     const int zb = n16 ? (int)std::min<size_t>((n16 + 1023) / 1024, 512) : 0;
     if (dtype != DT_BF16 && dtype != DT_F32) return MB_ERR_DTYPE;
-#define MB_HEAD_BWD(T, CH) hipLaunchKernelGGL((head_bwd_kernel<T, CH>), dim3(nb + zb), dim3(256), 0, st, dlogits, logits, labels, loss_scale, \
-                                              pooled, Wc, (T*)dz, dWc, dbc, B, nl, drop, acc, dbp, (u32x4*)zero_p, n16, nb)
+#define MB_HEAD_BWD_(T, CH, DEF) hipLaunchKernelGGL((head_bwd_kernel<T, CH, DEF>), dim3(nb + zb), dim3(256), 0, st, dlogits, logits, labels, loss_scale, \
+                                                    pooled, Wc, (T*)dz, dWc, dbc, B, nl, drop, acc, dbp, (u32x4*)zero_p, n16, nb, hl)
+#define MB_HEAD_BWD(T, CH) do { if (hl.kind == HL_DEFAULT) MB_HEAD_BWD_(T, CH, true); else MB_HEAD_BWD_(T, CH, false); } while (0)
 #define MB_HEAD_BWD_CH(CH) do { if (dtype == DT_BF16) MB_HEAD_BWD(bf16, CH); else MB_HEAD_BWD(float, CH); } while (0)
     switch (H / 256) { case 1: MB_HEAD_BWD_CH(1); break; case 2: MB_HEAD_BWD_CH(2); break; case 3: MB_HEAD_BWD_CH(3); break; default: MB_HEAD_BWD_CH(4); break; }
 #undef MB_HEAD_BWD_CH
 #undef MB_HEAD_BWD
+#undef MB_HEAD_BWD_
     return (int)hipGetLastError();
 }
 

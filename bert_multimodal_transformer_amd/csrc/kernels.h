@@ -287,14 +287,23 @@ int xlnet_unmap_vec(int dtype, const float* tm, const void* vec, void* vecg, int
 // ------------------------------------------------------------------------------------------ head (head.hip)
 // pooled = tanh(z) ; logits = dropout(pooled) Wc^T + bc ; optional MSE loss (mean over B*nl) accumulated into loss[0]
 // and (if non-null) into the running sum loss_run[0].
+// The objective (include/magbert_hip.h MB_LOSS_*): a kind, at most one scalar (smooth_l1's beta) and one device vector of nl floats
+// (bce's pos_weight, the cross entropy's class weights; null = none).  HL_DEFAULT is MSE at nl == 1 and cross entropy on class
+// indices otherwise, labels [B]; mse | l1 | smooth_l1 | bce read labels [B][nl]; HL_CE reads class indices [B] and needs nl >= 2
+// (MB_ERR_ARG otherwise, as for an unknown kind).
+enum { HL_DEFAULT = 0, HL_MSE = 1, HL_L1 = 2, HL_SMOOTH_L1 = 3, HL_BCE = 4, HL_CE = 5 };
+struct HeadLoss { int kind; float param; const float* vec; };
+inline bool head_loss_per_element(int kind) { return kind >= HL_MSE && kind <= HL_BCE; }
 int head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled,
-                 float* logits, float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st);
+                 float* logits, float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st,
+                 HeadLoss hl = HeadLoss{HL_DEFAULT, 0.f, nullptr});
 // dlogits (given, or MSE grad if labels != null: 2*(logit-y)/(B*nl)*loss_scale) -> dz (grad wrt pooler pre-activation),
 // dWc, dbc accumulated.  dz is written in the activation dtype (operand of the pooler dgrad / wgrad GEMMs).
 int head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale,
                   const float* pooled, const float* Wc, void* dz, float* dWc, float* dbc,
                   int B, int H, int nl, DropKey drop, hipStream_t st, GradAcc acc = {}, float* dbp = nullptr,
-                  void* zero_p = nullptr, size_t zero_bytes = 0);   // dbp += column sums of dz; zero_p[0, zero_bytes) cleared by extra blocks
+                  void* zero_p = nullptr, size_t zero_bytes = 0,    // dbp += column sums of dz; zero_p[0, zero_bytes) cleared by extra blocks
+                  HeadLoss hl = HeadLoss{HL_DEFAULT, 0.f, nullptr});  // the gradient of that objective where dlogits == null
 
 // ------------------------------------------------------------------------------------------ optimizer (adamw.hip)
 // transformers 3.0.2 AdamW over flat fp32 buffers; elements [0, n_decay) use weight_decay, the rest 0.

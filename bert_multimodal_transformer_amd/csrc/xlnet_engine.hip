@@ -262,6 +262,7 @@ void mb_xlnet_destroy(mb_xlnet_engine* e) {
     e->drop_graphs();
     e->free_class_table();
     e->free_clip_buf();
+    e->free_head_loss();
     delete e;
 }
 int mb_xlnet_num_tensors(const mb_xlnet_engine* e) { return (int)e->tensors.size(); }
@@ -389,8 +390,9 @@ static int xl_forward_range(mb_xlnet_engine* e, const int64_t* input_ids, const 
     CK(gemm(dt, GEMM_NT, EPI_BIAS_F32, B, H, H, ws + e->ws_xs, H, e->W(e->wsum), H, nullptr, H, nullptr, z, P + e->bsum, nullptr, 0,
             kNoDrop, 1, 64, st));
     if (loss && !(e->in_step && e->loss_cleared)) CK(zero_fill(loss, 4, st));
+    if (labels && !e->in_step) CK(e->sync_head_loss());          // (a step did this before its prologue, outside the capture)
     CK(head_forward(z, P + e->wc, P + e->bc, labels, (float*)(ws + e->ws_head_pooled), logits, loss, loss_run, B, H, c.num_labels,
-                    e->key(XS_HEAD, c.summary_last_dropout), st));
+                    e->key(XS_HEAD, c.summary_last_dropout), st, e->head_loss()));
     return MB_OK;
 }
 
@@ -443,9 +445,10 @@ int mb_xlnet_backward(mb_xlnet_engine* e, const float* dlogits, const float* lab
     };
     for (int stage = stage_begin; stage < stage_end; ++stage) {
         if (stage == 0) {
+            if (labels && !e->in_step) CK(e->sync_head_loss());
             CK(head_backward(dt, dlogits, e->logits, labels, loss_scale, (const float*)(ws + e->ws_head_pooled), P + e->wc,
                              ws + e->ws_dz, G + e->wc, G + e->bc, B, H, c.num_labels, e->key(XS_HEAD, c.summary_last_dropout), st,
-                             acc, G + e->bsum, ws + e->ws_dxa, (size_t)T * H * es));     // + summary bias gradient, + dx cleared
+                             acc, G + e->bsum, ws + e->ws_dxa, (size_t)T * H * es, e->head_loss()));     // + summary bias gradient, + dx cleared
             CK(gemm(dt, GEMM_TN, EPI_ACCUM_F32, H, H, B, ws + e->ws_dz, H, ws + e->ws_xs, H, nullptr, H, nullptr, G + e->wsum, nullptr,
                     nullptr, 0, kNoDrop, 1, 64, st));
             CK(gemm(dt, GEMM_NN, EPI_ADD_RES, B, H, H, ws + e->ws_dz, H, e->W(e->wsum), H, ws + e->ws_dxs, H, nullptr, nullptr, nullptr,
@@ -751,6 +754,14 @@ int mb_xlnet_set_head_mask(mb_xlnet_engine* e, const float* head_mask) {
     if (!e) return MB_ERR_ARG;
     e->head_mask = head_mask;
     return MB_OK;
+}
+int mb_xlnet_set_head_loss(mb_xlnet_engine* e, int kind, float param, const float* vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->set_head_loss(kind, param, vec, e->c.num_labels);
+}
+int mb_xlnet_get_head_loss(const mb_xlnet_engine* e, int* kind, float* param, float* vec, int* has_vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->get_head_loss(kind, param, vec, has_vec);
 }
 int mb_xlnet_set_profiling(mb_xlnet_engine* e, int on) {
     if (!e) return MB_ERR_ARG;

@@ -31,6 +31,7 @@ import torch.nn as nn
 from torch.nn import MSELoss
 from torch.utils.data import DataLoader, TensorDataset
 
+from . import losses as _head_losses
 from .bert import BertConfig, MAG_BertForSequenceClassification
 from .global_configs import DATASET_DIMS
 from .optimization import AdamW, get_linear_schedule_with_warmup, layerwise_lr_groups
@@ -131,6 +132,11 @@ def get_parser():
     parser.add_argument("--hidden_act", type=str, default=None, choices=sorted(_lib_activations()),
                         help="feed-forward activation of either model (BertConfig.hidden_act / XLNetConfig.ff_activation); default: "
                              "what the configuration says (gelu unless a checkpoint's config.json names another)")
+    parser.add_argument("--loss", type=str, default=None, choices=["mse", "l1", "smooth_l1"],
+                        help="the training objective of the fused head (model.set_loss), also what eval_epoch reports; default: the "
+                             "reference's MSE")
+    parser.add_argument("--loss_beta", type=float, default=None,
+                        help="beta of --loss smooth_l1 (default 1.0; 0 is l1)")
     parser.add_argument("--injection_index", type=int, default=None,
                         help="apply MAG in front of encoder layer N of either model (0 <= N < number of layers); default: 0 for the "
                              "BERT models (behind the embeddings, the reference) and XLNET_INJECTION_INDEX for the XLNet models")
@@ -454,6 +460,9 @@ def prep_for_training(num_train_optimization_steps: int):
             model = MAG_XLNetForSequenceClassification(with_hidden_act(xlnet_config(args.model), args.hidden_act), multimodal_config, visual_dim=V,
                                                        acoustic_dim=A, compute_dtype=dt, max_seq_length=args.max_seq_length, injection_index=inj)
     model.to(_device())
+    if getattr(args, "loss", None) is not None:
+        # (--loss_beta with another kind: set_loss's ValueError names what takes it)
+        model.set_loss(args.loss, beta=getattr(args, "loss_beta", None))
     if args.freeze_layers > 0 or args.freeze_embeddings:
         # the common fine-tuning recipe: the groups below leave the frozen parameters out, and the single-call step skips their work
         model.freeze(embeddings=args.freeze_embeddings, layers=args.freeze_layers)
@@ -514,7 +523,10 @@ def train_epoch(model: nn.Module, train_dataloader: DataLoader, optimizer, sched
             input_ids, visual, acoustic, input_mask, segment_ids, label_ids = _unpack(batch)
             outputs = model(input_ids, visual, acoustic, token_type_ids=segment_ids, attention_mask=input_mask, labels=None)
             logits = outputs[0]
-            loss = MSELoss()(logits.view(-1), label_ids.view(-1))
+            if getattr(args, "loss", None) is None:
+                loss = MSELoss()(logits.view(-1), label_ids.view(-1))
+            else:           # --loss: the objective the fused path runs, by torch
+                loss = _head_losses.torch_loss(model.loss, logits, label_ids, 1)
             if accum > 1:
                 loss = loss / accum
             if dp is not None:

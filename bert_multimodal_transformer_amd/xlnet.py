@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import losses as _losses
 from .bert import _BaseFn, _Core, _EngineFn, _FusedStep, _MagBertBase, _attach_parameters, _init_weights
 from .global_configs import ACOUSTIC_DIM, VISUAL_DIM, XLNET_INJECTION_INDEX
 
@@ -334,9 +335,6 @@ class MAG_XLNetForSequenceClassification(_FusedStep, _XlBase):
         if output_attentions:
             outputs = outputs + (tuple(a[:, :, mlen:] for a in core.xl_attentions(B, K, self.training)),)
         if labels is not None:                                        # xlnet.py:515-524
-            if self.num_labels == 1:
-                loss = torch.nn.functional.mse_loss(logits.view(-1), labels.to(logits.device).float().view(-1))
-            else:
-                loss = torch.nn.functional.cross_entropy(logits.view(-1, self.num_labels), labels.to(logits.device).view(-1))
+            loss = _losses.torch_loss(self._core.loss, logits, labels, self.num_labels)
             outputs = (loss,) + outputs
         return outputs

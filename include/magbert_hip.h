@@ -159,6 +159,27 @@ int mb_attention_tiled_backward(int dtype, const void* qkv, const int64_t* mask,
                                 void* dqkv, float* dbias, int B, int L, int nh, const mb_dropkey* drop, const float* head_scale,
                                 void* stream);
 
+/* The classification head with its fused objective (bert.py:304-322), as the engines launch it: one wave per sample.
+ *   pooled = tanh(z) [B][H] fp32; logits = dropout(pooled) Wc^T + bc [B][num_labels] fp32; H = 256 | 512 | 768 | 1024.
+ * The objective is a triple: loss_kind (MB_LOSS_*), loss_param (smooth_l1's beta, else ignored) and loss_vec, a DEVICE vector of
+ * num_labels floats or NULL (bce: pos_weight; cross_entropy: class weights; ignored by the other kinds).  Mean reduction throughout:
+ *   MB_LOSS_DEFAULT        labels [B]: MSE when num_labels == 1, else cross entropy on class indices held as floats
+ *   MB_LOSS_MSE | L1 | SMOOTH_L1 | BCE   labels [B][num_labels]; the mean runs over B * num_labels (bce targets lie in [0, 1])
+ *   MB_LOSS_CROSS_ENTROPY  labels [B] class indices, num_labels >= 2; with weights sum_b w[y_b] nll_b / sum_b w[y_b]
+ * (torch.nn.functional's mse_loss, l1_loss, smooth_l1_loss(beta), binary_cross_entropy_with_logits(pos_weight), cross_entropy(weight)).
+ * An unknown kind, or cross_entropy at num_labels == 1: MB_ERR_ARG.
+ * forward: labels NULL = no loss.  loss[0] += this batch's loss (the caller clears it), loss_run[0] += it too; either may be NULL.
+ * backward: the logit gradient is dlogits [B][num_labels] when given, else that of the objective (logits and labels required) times
+ * loss_scale.  dz [B][H] in `dtype` = the gradient of z; dWc [num_labels][H], dbc [num_labels], dbp [H] (+= column sums of dz), each
+ * fp32, accumulated, may be NULL; zero_p[0, zero_bytes) (16-byte multiples, may be NULL) is cleared by extra blocks of the launch. */
+enum { MB_LOSS_DEFAULT = 0, MB_LOSS_MSE = 1, MB_LOSS_L1 = 2, MB_LOSS_SMOOTH_L1 = 3, MB_LOSS_BCE = 4, MB_LOSS_CROSS_ENTROPY = 5 };
+int mb_head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits, float* loss,
+                    float* loss_run, int B, int H, int num_labels, const mb_dropkey* drop, int loss_kind, float loss_param,
+                    const float* loss_vec, void* stream);
+int mb_head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale, const float* pooled,
+                     const float* Wc, void* dz, float* dWc, float* dbc, float* dbp, void* zero_p, size_t zero_bytes, int B, int H,
+                     int num_labels, const mb_dropkey* drop, int loss_kind, float loss_param, const float* loss_vec, void* stream);
+
 /* Multimodal Adaptation Gate, MAG.forward (modeling.py:25-51) and its adjoint, for T tokens.
  * Parameters in the REFERENCE layout: W_hv [H][V+H], W_ha [H][A+H], W_v [H][V], W_a [H][A], biases [H], LayerNorm [H].
  * text [T][H] in `dtype`; visual [T][V], acoustic [T][A] fp32 (as the DataLoader yields them).
@@ -276,6 +297,16 @@ int mb_bert_set_attention_output(mb_bert_engine* e, float* probs);
  *   be NULL); the word table receives no gradient, and after the backward inputs_embeds_grad returns the gradient of the
  *   given embeddings, fp32 [B*L][H] (workspace memory, valid until the next backward). */
 int mb_bert_set_head_mask(mb_bert_engine* e, const float* head_mask);
+/* The objective of every pass that is given labels (mb_head_forward above describes the triple): the explicit forward / backward,
+ * the stage-driven passes, mb_bert_train_step and its graph, the data-parallel steps.  vec: HOST pointer to num_labels floats or NULL,
+ * copied.  Sticky like head_mask, legal between steps; an engine starts with MB_LOSS_DEFAULT.  Under the per-element kinds `labels`
+ * holds B * num_labels floats everywhere, mb_bert_load_batch's staging included.  Checked before any device call -- MB_ERR_ARG for an
+ * unknown kind, cross_entropy at num_labels == 1, a beta that is negative or not finite, a weight that is negative or not finite, all
+ * weights zero, a vector handed to a kind that takes none.  A change drops the engine's captured graphs (kind and scalar are kernel
+ * arguments): the next step captures again and runs the new objective.  The workspace is not involved.
+ * get: what is set; vec (num_labels floats, may be NULL) is written only when *has_vec comes back 1. */
+int mb_bert_set_head_loss(mb_bert_engine* e, int kind, float param, const float* vec);
+int mb_bert_get_head_loss(const mb_bert_engine* e, int* kind, float* param, float* vec, int* has_vec);
 int mb_bert_set_inputs_embeds(mb_bert_engine* e, const float* inputs_embeds);
 /* position_ids (bert.py:211-216): int64 [B*L] device tensor of position-table rows for the next forwards / backwards, NULL =
  * BertEmbeddings' default arange(seq_len).  Sticky like head_mask; the single-call step refuses to run while it is set. */
@@ -527,6 +558,8 @@ int mb_xlnet_attention_probs_into(mb_xlnet_engine* e, int layer, float* out, voi
  * contributes head_mask[l][h] times its attention output (attn_prob * head_mask after the dropout).  Explicit forwards /
  * backwards only: mb_xlnet_train_step returns MB_ERR_MODE while it is set. */
 int mb_xlnet_set_head_mask(mb_xlnet_engine* e, const float* head_mask);
+int mb_xlnet_set_head_loss(mb_xlnet_engine* e, int kind, float param, const float* vec);      /* as mb_bert_set_head_loss; the query-stream head has no loss */
+int mb_xlnet_get_head_loss(const mb_xlnet_engine* e, int* kind, float* param, float* vec, int* has_vec);
 /* perm_mask / input_mask (xlnet.py:258-296): bytes [B][L][L] in device memory, sticky until reset with NULL; perm[b][i][j] != 0 <=>
  * data_mask[i, j, b] = input_mask[j, b] + perm_mask[i, j, b] > 0, i.e. query i may not attend to key j (i == j is always allowed:
  * non_tgt_mask, xlnet.py:288-296).  Combined with the attention_mask argument of the passes by OR.  Explicit forwards /

@@ -22,6 +22,7 @@
 //            (mb_*_set_update_frozen): no weight-gradient launch for those layers, no embedding backward; composes with --layer_decay and
 //            --max_grad_norm.  Without --layer_decay the rest is the two parameter groups as a two-class map.  Prints mb_*_freeze_stats.
 //   --act gelu|relu|swish|silu|gelu_new|mish: the feed-forward activation (mb_bert_config.hidden_act / mb_xlnet_config.ff_activation)
+//   --loss default|mse|l1|smooth_l1 [--loss_beta X]: the head's objective (mb_*_set_head_loss; the run stays at num_labels = 1)
 //   --inject N: MAG in front of encoder layer N (injection_index of either config; default 0 for MAG-BERT, 1 for MAG-XLNet)
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
@@ -54,6 +55,7 @@ int main(int argc, char** argv) {
     int freeze_layers = 0, freeze_emb = 0, act = MB_ACT_GELU, inject = -1;      // --inject N: MAG in front of layer N (default: 0 | MAG-XLNet: 1)
     int all_live = 0;           // --all_live 1: every sample has L - 2 words (no padding token: the worst case of the live-row weight gradients)
     const char* act_name = "gelu";
+    int loss_kind = MB_LOSS_DEFAULT; double loss_beta = 1.0; const char* loss_name = "default";
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -76,9 +78,17 @@ int main(int argc, char** argv) {
             if (act < 0) { fprintf(stderr, "--act: gelu | relu | swish | silu | gelu_new | mish\n"); return 1; }
             act_name = v;
         }
+        else if (k == "--loss") {
+            const char* names[] = {"default", "mse", "l1", "smooth_l1"};
+            loss_kind = -1;
+            for (int a = 0; a < 4; ++a) if (strcmp(v, names[a]) == 0) loss_kind = a;
+            if (loss_kind < 0) { fprintf(stderr, "--loss: default | mse | l1 | smooth_l1\n"); return 1; }
+            loss_name = v;
+        }
+        else if (k == "--loss_beta") loss_beta = atof(v);
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --inject --all_live)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --loss --loss_beta --inject --all_live)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
@@ -106,6 +116,10 @@ int main(int argc, char** argv) {
         MCK(mb_bert_create(&c, &e));
         n = mb_bert_param_count(e); nd = mb_bert_decay_count(e); wsb = mb_bert_workspace_bytes(e);
         mb_bert_shadow_range(e, &shb, &she);
+    }
+    if (loss_kind != MB_LOSS_DEFAULT) {
+        const float beta = loss_kind == MB_LOSS_SMOOTH_L1 ? (float)loss_beta : 0.f;
+        if (xl) MCK(mb_xlnet_set_head_loss(ex, loss_kind, beta, nullptr)); else MCK(mb_bert_set_head_loss(e, loss_kind, beta, nullptr));
     }
     float *P, *G, *M, *Vv; void *SH, *WS;
     HCK(hipMalloc(&P, n * 4)); HCK(hipMalloc(&G, n * 4)); HCK(hipMalloc(&M, n * 4)); HCK(hipMalloc(&Vv, n * 4));
@@ -280,6 +294,7 @@ int main(int argc, char** argv) {
     char shape[96] = "";
     if ((hidden != 768 || heads != 12 || inter != 3072)) snprintf(shape, sizeof shape, " hidden=%d heads=%d inter=%d", hidden, heads, inter);
     if (act != MB_ACT_GELU) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " act=%s", act_name);
+    if (loss_kind != MB_LOSS_DEFAULT) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " loss=%s", loss_name);
     printf("step_bench %sdtype=%s B=%d L=%d V=%d layers=%d%s graph=%d h2d=%d : %.3f ms/step (events) %.3f ms/step (wall) host-enqueue %.3f ms/step "
            "%.1f samples/s last-loss %.4f mean-loss %.4f\n",
            xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, shape, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
