@@ -97,6 +97,11 @@ PROTOTYPES = {
     "mb_mag_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mb_mag_forward": (_i, [_i] + [_vp] * 13 + [_f, _dk, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mb_mag_backward": (_i, [_i] + [_vp] * 11 + [_f, _dk] + [_vp] * 14 + [_i, _i, _i, _i, _vp]),
+    # test hooks (tests/mag_op_helpers.py): MAG as the engines call it (padded text, caller-kept pad rows, slabs, stored weight gradients)
+    "mb_debug_mag_forward_ex": (_i, [_i] + [_vp] * 13 + [_f, _dk, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mb_debug_mag_slab_bytes": (_sz, [_i, _i]),
+    "mb_debug_mag_backward_ex": (_i, [_i] + [_vp] * 7 + [_f, _dk] + [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i,
+                                      C.POINTER(_i), _vp]),
     "mb_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _f, _f, _f, _f, _f, _i, _i, _f, _i, _vp]),
     "mb_bert_create": (_i, [C.POINTER(BertEngineConfig), C.POINTER(_vp)]),
     "mb_bert_destroy": (None, [_vp]),

@@ -540,12 +540,49 @@ int mb_mag_backward(int dtype, const void* d_out, const void* text, const float*
                     float* dW_v, float* db_v, float* dW_a, float* db_a, float* dln_w, float* dln_b, int T, int H, int V,
                     int A, void* stream) {
     (void)W_hv; (void)W_ha; (void)W_v; (void)W_a;   // the packed copies made by the forward are reused
-    if (H % 256 || H < 256 || H > 1024) return MB_ERR_SHAPE;
+    if (H % 256 || H < 256 || H > 1024 || V < 1 || A < 1) return MB_ERR_SHAPE;
     MagWs w;
     w.init(dtype, T, H, V, A);
     return mag_bwd_impl(dtype, d_out, text, b_hv, b_ha, b_v, b_a, ln_w, beta_shift, dk(drop), (char*)ws, w, d_text,
                         d_visual, d_acoustic, dW_hv, db_hv, dW_ha, db_ha, dW_v, db_v, dW_a, db_a, dln_w, dln_b, T, H, V, A,
                         false, (hipStream_t)stream);
+}
+
+// test hooks (tests/mag_op_helpers.py): the two MAG implementations with the arguments only the engines set
+int mb_debug_mag_forward_ex(int dtype, const void* text, const float* visual, const float* acoustic, const float* W_hv,
+                            const float* b_hv, const float* W_ha, const float* b_ha, const float* W_v, const float* b_v,
+                            const float* W_a, const float* b_a, const float* ln_w, const float* ln_b, float beta_shift,
+                            const mb_dropkey* drop, void* out, void* ws, int T, int H, int V, int A, int pads_clean, void* stream) {
+    if (H % 256 || H < 256 || H > 1024 || V < 1 || A < 1) return MB_ERR_SHAPE;
+    MagWs w;
+    w.init(dtype, T, H, V, A);
+    return mag_fwd_impl(dtype, text, visual, acoustic, W_hv, b_hv, W_ha, b_ha, W_v, b_v, W_a, b_a, ln_w, ln_b, 1e-5f,
+                        beta_shift, dk(drop), out, (char*)ws, w, T, H, V, A, true, (hipStream_t)stream, pads_clean != 0);
+}
+size_t mb_debug_mag_slab_bytes(int T, int H) { return T < 1 ? 0 : (size_t)2 * ((T + 7) / 8) * 3 * H * sizeof(float); }
+int mb_debug_mag_backward_ex(int dtype, const void* d_out, const void* text, const float* b_hv, const float* b_ha, const float* b_v,
+                             const float* b_a, const float* ln_w, float beta_shift, const mb_dropkey* drop, void* ws, void* d_text,
+                             float* d_visual, float* d_acoustic, float* dW_hv, float* db_hv, float* dW_ha, float* db_ha,
+                             float* dW_v, float* db_v, float* dW_a, float* db_a, float* dln_w, float* dln_b, int T, int H, int V,
+                             int A, int text_padded, int pads_clean, int slabs, float* slab_scratch, size_t slab_bytes, int dw_zero,
+                             int* path, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (H % 256 || H < 256 || H > 1024 || V < 1 || A < 1) return MB_ERR_SHAPE;
+    if (slabs && (!slab_scratch || slab_bytes < mb_debug_mag_slab_bytes(T, H))) return MB_ERR_ARG;
+    MagWs w;
+    w.init(dtype, T, H, V, A);
+    // the two partial sets [blocks][3][H], one behind the other (the engines: slot NL of ws_lnp_a / ws_lnp_b)
+    float* pa = slabs ? slab_scratch : nullptr;
+    float* pb = slabs ? slab_scratch + mb_debug_mag_slab_bytes(T, H) / (2 * sizeof(float)) : nullptr;
+    int nblk = 0;
+    CK(mag_bwd_impl(dtype, d_out, text, b_hv, b_ha, b_v, b_a, ln_w, beta_shift, dk(drop), (char*)ws, w, d_text, d_visual,
+                    d_acoustic, dW_hv, db_hv, dW_ha, db_ha, dW_v, db_v, dW_a, db_a, dln_w, dln_b, T, H, V, A, text_padded != 0, st,
+                    GradAcc{}, pads_clean != 0, pa, pb, &nblk, dw_zero != 0, path));
+    if (slabs) {
+        float* const m6[6] = {db_hv, db_ha, db_v, db_a, dln_w, dln_b};
+        CK(ln_reduce_partials(pa, pb, nblk, H, m6, st, GradAcc{}));
+    }
+    return MB_OK;
 }
 
 int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, size_t n_decay, size_t sh_begin,

@@ -1011,8 +1011,9 @@ inline int mag_bwd_impl(int dtype, const void* d_out, const void* text, const fl
                  float* d_visual, float* d_acoustic, float* dW_hv, float* db_hv, float* dW_ha, float* db_ha, float* dW_v,
                  float* db_v, float* dW_a, float* db_a, float* dln_w, float* dln_b, int T, int H, int V, int A,
                  bool text_padded, hipStream_t st, GradAcc acc = {}, bool pads_clean = false, float* part_a = nullptr,
-                 float* part_b = nullptr, int* part_nblk = nullptr, bool dw_zero = false) {
+                 float* part_b = nullptr, int* part_nblk = nullptr, bool dw_zero = false, int* path = nullptr) {
     // dw_zero: the caller knows the four weight-gradient tensors hold zeros (the engines' store path): plain stores, no read-modify-write
+    // path (test hook mb_debug_mag_backward_ex only): three ints out -- grouped launch or not, direct stores or not, tile
     MagDims d = {T, H, V, A, w.Vp, w.Ap};
     const int Tp = (int)align_up((size_t)T, 64);      // zero-padded token rows of the workspace operands
     const size_t es = esize(dtype);
@@ -1035,6 +1036,7 @@ inline int mag_bwd_impl(int dtype, const void* d_out, const void* text, const fl
     const int wtile = (w.Vp % 128 == 0 && w.Ap % 128 == 0 && H % 128 == 0 && mag_wgrad_tile() == 128 && gemm_grouped_tn_ok(dtype, wg, 3, 128)) ? 128 : 64;
     const bool grouped = text_padded && gemm_grouped_tn_ok(dtype, wg, 3, wtile);
     const bool direct = grouped && direct_env != 0;
+    if (path) { path[0] = grouped ? 1 : 0; path[1] = direct ? 1 : 0; path[2] = wtile; }
     if (direct) {
         const size_t half = (size_t)H * es;          // the projection half of a dZ row starts H columns in
         wg[0] = wgrad_args(H, H, Kt, dZe, 2 * H, text, H, dW_hv + V, V + H);                 wg[0].cvalid = H;

@@ -197,6 +197,28 @@ int mb_mag_backward(int dtype, const void* d_out, const void* text, const float*
                     void* d_text, float* d_visual, float* d_acoustic, float* dW_hv, float* db_hv, float* dW_ha,
                     float* db_ha, float* dW_v, float* db_v, float* dW_a, float* db_a, float* dln_w, float* dln_b,
                     int T, int H, int V, int A, void* stream);
+/* TEST HOOKS (tests/mag_op_helpers.py; no engine code calls them): the same two implementations with the arguments only the engines set.
+ * mb_debug_mag_forward_ex = mb_mag_forward plus
+ *   pads_clean    the caller keeps rows [T, align_up(T, 64)) of the workspace's packed modality operands zero itself
+ * mb_debug_mag_backward_ex = mb_mag_backward (without the four weights it never reads) plus
+ *   text_padded   `text` has align_up(T, 64) rows (rows behind T meet zero rows of the three dZ panels)
+ *   pads_clean    the caller keeps the pad rows of the packed modalities and of the three dZ panels zero itself
+ *   slabs         the six column sums (db_hv, db_ha, db_v, db_a, dln_w, dln_b) go to per-block slabs in slab_scratch (device memory of
+ *                 at least mb_debug_mag_slab_bytes(T, H), else MB_ERR_ARG) and one reduction launch adds them up, as in the engines
+ *   dw_zero       the four weight gradients are stored, not accumulated (the caller says they hold zeros)
+ *   path          may be NULL: three ints out -- 1 when the weight gradients ran as one grouped launch, 1 when that launch stored
+ *                 straight into dW_hv / dW_ha / dW_v / dW_a, and its tile (64 | 128) */
+int mb_debug_mag_forward_ex(int dtype, const void* text, const float* visual, const float* acoustic, const float* W_hv,
+                            const float* b_hv, const float* W_ha, const float* b_ha, const float* W_v, const float* b_v,
+                            const float* W_a, const float* b_a, const float* ln_w, const float* ln_b, float beta_shift,
+                            const mb_dropkey* drop, void* out, void* ws, int T, int H, int V, int A, int pads_clean, void* stream);
+size_t mb_debug_mag_slab_bytes(int T, int H);
+int mb_debug_mag_backward_ex(int dtype, const void* d_out, const void* text, const float* b_hv, const float* b_ha, const float* b_v,
+                             const float* b_a, const float* ln_w, float beta_shift, const mb_dropkey* drop, void* ws, void* d_text,
+                             float* d_visual, float* d_acoustic, float* dW_hv, float* db_hv, float* dW_ha, float* db_ha,
+                             float* dW_v, float* db_v, float* dW_a, float* db_a, float* dln_w, float* dln_b, int T, int H, int V,
+                             int A, int text_padded, int pads_clean, int slabs, float* slab_scratch, size_t slab_bytes, int dw_zero,
+                             int* path, void* stream);
 
 /* transformers 3.0.2 AdamW.step over flat fp32 buffers (multimodal_driver.py:345,384). [0,n_decay) decays.
  * shadow: optional bf16 copy of p written for [sh_begin, sh_end).  zero_grad != 0 clears g (optimizer.zero_grad). */
