@@ -64,6 +64,19 @@ class XlnetEngineConfig(C.Structure):
                 ("dtype", C.c_int), ("max_batch", C.c_int), ("max_seq", C.c_int), ("ff_activation", C.c_int)]
 
 
+class HeadLossStruct(C.Structure):
+    """mb_head_loss (include/magbert_hip.h): the head's objective with its options; vec a device pointer for the operator entries
+    (mb_head_forward_ex / mb_head_backward_ex), a host pointer for the engines' setters"""
+    _fields_ = [("kind", C.c_int), ("param", C.c_float), ("vec", C.c_void_p), ("label_smoothing", C.c_float), ("focal_gamma", C.c_float),
+                ("has_ignore_index", C.c_int), ("ignore_index", C.c_int)]
+
+
+def head_loss_struct(kind, param=0.0, vec=None, label_smoothing=None, focal_gamma=None, ignore_index=None):
+    """vec: an address (int / c_void_p) or None; None options are neutral"""
+    return HeadLossStruct(int(kind), float(param or 0.0), vec, float(label_smoothing or 0.0), float(focal_gamma or 0.0),
+                          0 if ignore_index is None else 1, 0 if ignore_index is None else int(ignore_index))
+
+
 _vp, _i, _f, _sz, _u64, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64, C.c_uint32
 _dk = C.POINTER(DropKey)
 
@@ -87,6 +100,12 @@ PROTOTYPES = {
     "mb_attention_resident_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _vp, _vp]),
     "mb_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, _i, _f, _vp, _vp]),
     "mb_head_backward": (_i, [_i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _dk, _i, _f, _vp, _vp]),
+    "mb_head_forward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dk, C.POINTER(HeadLossStruct), _vp]),
+    "mb_head_backward_ex": (_i, [_i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _dk, C.POINTER(HeadLossStruct), _vp]),
+    "mb_bert_set_head_loss_ex": (_i, [_vp, C.POINTER(HeadLossStruct)]),
+    "mb_bert_get_head_loss_ex": (_i, [_vp, C.POINTER(HeadLossStruct), _vp, C.POINTER(_i)]),
+    "mb_xlnet_set_head_loss_ex": (_i, [_vp, C.POINTER(HeadLossStruct)]),
+    "mb_xlnet_get_head_loss_ex": (_i, [_vp, C.POINTER(HeadLossStruct), _vp, C.POINTER(_i)]),
     "mb_bert_set_head_loss": (_i, [_vp, _i, _f, _vp]),
     "mb_bert_get_head_loss": (_i, [_vp, C.POINTER(_i), C.POINTER(_f), _vp, C.POINTER(_i)]),
     "mb_xlnet_set_head_loss": (_i, [_vp, _i, _f, _vp]),

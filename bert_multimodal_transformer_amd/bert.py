@@ -271,11 +271,13 @@ class _Core(object):
 
     def _apply_loss(self):
         vec = self.loss.vector
-        arr = None if vec is None else (C.c_float * len(vec))(*vec)
-        _lib.check(self._fn("set_head_loss")(self.handle, self.loss.code, float(self.loss.beta or 0.0), arr))
+        arr = None if vec is None else (C.c_float * len(vec))(*vec)             # (kept alive until the call returns: the engine copies)
+        hl = _lib.head_loss_struct(self.loss.code, self.loss.beta, None if arr is None else C.addressof(arr), self.loss.label_smoothing,
+                                   self.loss.focal_gamma, self.loss.ignore_index)
+        _lib.check(self._fn("set_head_loss_ex")(self.handle, C.byref(hl)))
 
     def set_loss(self, loss):
-        """a checked losses.HeadLoss -> this core and its engine (include/magbert_hip.h: mb_*_set_head_loss; sticky, between steps)"""
+        """a checked losses.HeadLoss -> this core and its engine (include/magbert_hip.h: mb_*_set_head_loss_ex; sticky, between steps)"""
         old, self.loss = self.loss, loss
         try:
             self._apply_loss()
@@ -1043,8 +1045,10 @@ class _MagBertBase(nn.Module):
         multimodal_config = kwargs.pop("multimodal_config", model_args[0] if model_args else None)
         num_labels = kwargs.pop("num_labels", 1)
         want_info = kwargs.pop("output_loading_info", False)
-        # the head's objective: set_loss's arguments as keywords (loss="l1", beta=..., pos_weight=..., weight=...)
-        loss_kw = {k: kwargs.pop(k) for k in ("loss", "beta", "pos_weight", "weight") if k in kwargs}
+        # the head's objective: set_loss's arguments as keywords (loss="l1", beta=..., pos_weight=..., weight=..., label_smoothing=...,
+        # ignore_index=..., focal_gamma=...)
+        loss_kw = {k: kwargs.pop(k) for k in ("loss", "beta", "pos_weight", "weight", "label_smoothing", "ignore_index", "focal_gamma")
+                   if k in kwargs}
         # no config given: the `config.json` next to the checkpoint says which model it is (a bert-large directory loads as
         # bert-large); without one it is bert-base-uncased, as before
         config = config or cls._config_beside(pretrained_model_name_or_path, num_labels) or cls._default_config(num_labels)
@@ -1052,7 +1056,8 @@ class _MagBertBase(nn.Module):
         model = cls(config, multimodal_config, **kwargs)
         if loss_kw:
             if not hasattr(model, "set_loss"):
-                raise ValueError("%s has no head: loss / beta / pos_weight / weight belong to the *ForSequenceClassification classes" % cls.__name__)
+                raise ValueError("%s has no head: loss / beta / pos_weight / weight / label_smoothing / ignore_index / focal_gamma belong to "
+                                 "the *ForSequenceClassification classes" % cls.__name__)
             model.set_loss(loss_kw.pop("loss", "default"), **loss_kw)
         path = _pretrained_file(pretrained_model_name_or_path, cls.__name__)
         sd = torch.load(path, map_location="cpu")
@@ -1076,18 +1081,24 @@ class _FusedStep(object):
     """Fused training surface shared by MAG_BertForSequenceClassification and MAG_XLNetForSequenceClassification
     (what the bundled driver's train_epoch and bench.py call instead of the reference's five-line step)."""
 
-    def set_loss(self, name, beta=None, pos_weight=None, weight=None):
+    def set_loss(self, name, beta=None, pos_weight=None, weight=None, label_smoothing=None, ignore_index=None, focal_gamma=None):
         """The objective of every pass that is given labels -- training_step, train_step and its graph, stage_step, eval_step, the
         data-parallel steps, and forward(labels=...) on the autograd route: "default" (MSE at num_labels == 1, else cross entropy: the
         reference's classes), "mse", "l1", "smooth_l1" (beta, default 1.0; 0 is l1), "bce" (pos_weight: num_labels values or None) and
         "cross_entropy" (weight: num_labels class weights or None; num_labels >= 2) -- torch.nn.functional's functions of those names
         under mean reduction.  mse / l1 / smooth_l1 / bce take label_ids of shape [B, num_labels], the others [B].  Sticky, legal
-        between steps; an unknown name or an argument that does not belong to the kind raises ValueError."""
-        self._core.set_loss(_losses.make_loss(name, int(self.config.num_labels), beta=beta, pos_weight=pos_weight, weight=weight))
+        between steps; an unknown name or an argument that does not belong to the kind raises ValueError.
+        Options: cross_entropy takes label_smoothing (in [0, 1)), ignore_index (an integer: samples with that label count for nothing,
+        and the mean runs over the class weights -- or the count -- of the others) and focal_gamma (0, or >= 1; not together with
+        label_smoothing); bce takes focal_gamma (the sigmoid focal loss).  Where every kept sample has weight 0 the loss and its
+        gradients are 0 (torch: NaN); a batch whose every label is ignored is refused on the host (losses.py has the details and
+        what is not built)."""
+        self._core.set_loss(_losses.make_loss(name, int(self.config.num_labels), beta=beta, pos_weight=pos_weight, weight=weight,
+                                              label_smoothing=label_smoothing, ignore_index=ignore_index, focal_gamma=focal_gamma))
 
     @property
     def loss(self):
-        """what set_loss installed (losses.HeadLoss: name, beta, pos_weight, weight)"""
+        """what set_loss installed (losses.HeadLoss: name, beta, pos_weight, weight, label_smoothing, ignore_index, focal_gamma)"""
         return self._core.loss
 
     def training_step(self, input_ids, visual, acoustic, attention_mask, token_type_ids, label_ids, loss_scale=1.0):

@@ -492,6 +492,22 @@ int mb_head_backward(int dtype, const float* dlogits, const float* logits, const
     return head_backward(dtype, dlogits, logits, labels, loss_scale, pooled, Wc, dz, dWc, dbc, B, H, num_labels, dk(drop),
                          (hipStream_t)stream, GradAcc{}, dbp, zero_p, zero_bytes, HeadLoss{loss_kind, loss_param, loss_vec});
 }
+static HeadLoss head_loss_of(const mb_head_loss* hl) {
+    return HeadLoss{hl->kind, hl->param, hl->vec, hl->label_smoothing, hl->focal_gamma, hl->has_ignore_index ? hl->ignore_index : 0,
+                    hl->has_ignore_index ? 1 : 0};
+}
+int mb_head_forward_ex(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits, float* loss,
+                       float* loss_run, int B, int H, int num_labels, const mb_dropkey* drop, const mb_head_loss* hl, void* stream) {
+    if (!z || !Wc || !bc || !pooled || !logits || B < 0 || num_labels < 1 || !hl) return MB_ERR_ARG;
+    return head_forward(z, Wc, bc, labels, pooled, logits, loss, loss_run, B, H, num_labels, dk(drop), (hipStream_t)stream, head_loss_of(hl));
+}
+int mb_head_backward_ex(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale, const float* pooled,
+                        const float* Wc, void* dz, float* dWc, float* dbc, float* dbp, void* zero_p, size_t zero_bytes, int B, int H,
+                        int num_labels, const mb_dropkey* drop, const mb_head_loss* hl, void* stream) {
+    if (!pooled || !Wc || !dz || B < 0 || num_labels < 1 || !hl) return MB_ERR_ARG;
+    return head_backward(dtype, dlogits, logits, labels, loss_scale, pooled, Wc, dz, dWc, dbc, B, H, num_labels, dk(drop),
+                         (hipStream_t)stream, GradAcc{}, dbp, zero_p, zero_bytes, head_loss_of(hl));
+}
 
 int mb_attention_resident_forward(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int nh,
                                   const mb_dropkey* drop, const float* head_scale, float* probs, void* stream) {
@@ -1336,6 +1352,14 @@ int mb_bert_set_head_loss(mb_bert_engine* e, int kind, float param, const float*
 int mb_bert_get_head_loss(const mb_bert_engine* e, int* kind, float* param, float* vec, int* has_vec) {
     if (!e) return MB_ERR_ARG;
     return e->get_head_loss(kind, param, vec, has_vec);
+}
+int mb_bert_set_head_loss_ex(mb_bert_engine* e, const mb_head_loss* hl) {
+    if (!e || !hl) return MB_ERR_ARG;
+    return e->set_head_loss_ex(*hl, e->c.num_labels);
+}
+int mb_bert_get_head_loss_ex(const mb_bert_engine* e, mb_head_loss* hl, float* vec, int* has_vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->get_head_loss_ex(hl, vec, has_vec);
 }
 int mb_bert_set_inputs_embeds(mb_bert_engine* e, const float* inputs_embeds) {
     if (!e) return MB_ERR_ARG;

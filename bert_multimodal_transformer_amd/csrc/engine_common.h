@@ -743,12 +743,22 @@ struct StepMixin {
     // any device call.  kind and scalar are kernel arguments, baked into every captured graph that holds a head launch: a change drops the
     // engine's graphs (the next step captures again).  The vector lives in device memory of the engine's own, like class_table -- never
     // the workspace -- and is uploaded by the first pass after the setter, outside any capture (sync_head_loss).
+    // The options of mb_head_loss (smoothing, focal gamma, ignored label) are kernel arguments like the kind; set_head_loss clears them.
     int loss_kind = HL_DEFAULT; float loss_param = 0.f;
+    float loss_smoothing = 0.f, loss_gamma = 0.f; int loss_ignore = 0, loss_has_ignore = 0;
     std::vector<float> loss_vec;             // host copy (empty = none)
     float* loss_vec_dev = nullptr; size_t loss_vec_cap = 0; bool loss_vec_dirty = false;
     size_t label_floats(int B, int num_labels) const { return (size_t)B * (head_loss_per_element(loss_kind) ? num_labels : 1); }
-    HeadLoss head_loss() const { return HeadLoss{loss_kind, loss_param, loss_vec.empty() ? nullptr : loss_vec_dev}; }
+    HeadLoss head_loss() const {
+        return HeadLoss{loss_kind, loss_param, loss_vec.empty() ? nullptr : loss_vec_dev, loss_smoothing, loss_gamma, loss_ignore, loss_has_ignore};
+    }
     int set_head_loss(int kind, float param, const float* vec, int num_labels) {
+        return set_head_loss_ex(mb_head_loss{kind, param, vec, 0.f, 0.f, 0, 0}, num_labels);
+    }
+    int set_head_loss_ex(const mb_head_loss& in, int num_labels) {
+        const int kind = in.kind; float param = in.param; const float* vec = in.vec;
+        const int has_ignore = in.has_ignore_index ? 1 : 0, ignore = has_ignore ? in.ignore_index : 0;
+        if (!head_loss_legal(HeadLoss{kind, param, nullptr, in.label_smoothing, in.focal_gamma, ignore, has_ignore}, num_labels)) return MB_ERR_ARG;
         if (kind < HL_DEFAULT || kind > HL_CE) return MB_ERR_ARG;
         if (kind == HL_CE && num_labels < 2) return MB_ERR_ARG;
         if (kind == HL_SMOOTH_L1 && !(std::isfinite(param) && param >= 0.f)) return MB_ERR_ARG;
@@ -765,10 +775,12 @@ struct StepMixin {
         if (kind != HL_SMOOTH_L1) param = 0.f;
         std::vector<float> nv;
         if (vec) nv.assign(vec, vec + num_labels);
-        if (kind == loss_kind && param == loss_param && nv == loss_vec) return MB_OK;
+        if (kind == loss_kind && param == loss_param && nv == loss_vec && in.label_smoothing == loss_smoothing && in.focal_gamma == loss_gamma &&
+            has_ignore == loss_has_ignore && ignore == loss_ignore) return MB_OK;
         // graphs in flight read the old arguments (and the old vector): wait for them before they go
         if (!graphs.empty() || !stage_graphs.empty()) { CK((int)hipDeviceSynchronize()); drop_graphs(); }
         loss_kind = kind; loss_param = param;
+        loss_smoothing = in.label_smoothing; loss_gamma = in.focal_gamma; loss_has_ignore = has_ignore; loss_ignore = ignore;
         loss_vec_dirty = loss_vec_dirty || nv != loss_vec;
         loss_vec.swap(nv);
         return MB_OK;
@@ -779,6 +791,10 @@ struct StepMixin {
         if (has_vec) *has_vec = loss_vec.empty() ? 0 : 1;
         if (vec) std::copy(loss_vec.begin(), loss_vec.end(), vec);
         return MB_OK;
+    }
+    int get_head_loss_ex(mb_head_loss* hl, float* vec, int* has_vec) const {
+        if (hl) *hl = mb_head_loss{loss_kind, loss_param, nullptr, loss_smoothing, loss_gamma, loss_has_ignore, loss_ignore};
+        return get_head_loss(nullptr, nullptr, vec, has_vec);
     }
     // the vector on the device before a head launch reads it (never inside a capture: the passes call it before they enqueue)
     int sync_head_loss() {

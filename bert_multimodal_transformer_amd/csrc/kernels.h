@@ -291,8 +291,23 @@ int xlnet_unmap_vec(int dtype, const float* tm, const void* vec, void* vecg, int
 // (bce's pos_weight, the cross entropy's class weights; null = none).  HL_DEFAULT is MSE at nl == 1 and cross entropy on class
 // indices otherwise, labels [B]; mse | l1 | smooth_l1 | bce read labels [B][nl]; HL_CE reads class indices [B] and needs nl >= 2
 // (MB_ERR_ARG otherwise, as for an unknown kind).
+// Modifiers (mb_head_loss of include/magbert_hip.h; all zero = none, and then the launch is the one it always was): HL_CE takes
+// `smoothing` (label smoothing, [0, 1)), `ignore` under `has_ignore` (samples whose label equals it count for nothing) and `gamma`
+// (focal, 0 or >= 1, not with smoothing); HL_BCE takes `gamma`.  Anything else: MB_ERR_ARG.  The cross entropy is normalised by the
+// class weights -- or the count -- of the kept samples; where that is 0 the loss and every gradient are 0 (torch: NaN).
 enum { HL_DEFAULT = 0, HL_MSE = 1, HL_L1 = 2, HL_SMOOTH_L1 = 3, HL_BCE = 4, HL_CE = 5 };
-struct HeadLoss { int kind; float param; const float* vec; };
+struct HeadLoss { int kind; float param; const float* vec; float smoothing; float gamma; int ignore; int has_ignore; };
+inline bool head_loss_modified(const HeadLoss& hl) { return hl.smoothing != 0.f || hl.gamma != 0.f || hl.has_ignore != 0; }
+// what the kernels and the engines' setters take (no pointer is followed)
+inline bool head_loss_legal(const HeadLoss& hl, int nl) {
+    if (hl.kind < HL_DEFAULT || hl.kind > HL_CE || (hl.kind == HL_CE && nl < 2)) return false;
+    if (!(hl.smoothing >= 0.f && hl.smoothing < 1.f)) return false;                          // (NaN fails both)
+    if (!(hl.gamma == 0.f || (hl.gamma >= 1.f && hl.gamma <= 3.402823466e38f))) return false;       // 0, or finite and >= 1
+    if (hl.smoothing > 0.f && hl.gamma > 0.f) return false;
+    if ((hl.smoothing > 0.f || hl.has_ignore) && hl.kind != HL_CE) return false;
+    if (hl.gamma > 0.f && hl.kind != HL_CE && hl.kind != HL_BCE) return false;
+    return true;
+}
 inline bool head_loss_per_element(int kind) { return kind >= HL_MSE && kind <= HL_BCE; }
 int head_forward(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled,
                  float* logits, float* loss, float* loss_run, int B, int H, int nl, DropKey drop, hipStream_t st,

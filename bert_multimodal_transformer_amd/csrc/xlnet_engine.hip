@@ -763,6 +763,14 @@ int mb_xlnet_get_head_loss(const mb_xlnet_engine* e, int* kind, float* param, fl
     if (!e) return MB_ERR_ARG;
     return e->get_head_loss(kind, param, vec, has_vec);
 }
+int mb_xlnet_set_head_loss_ex(mb_xlnet_engine* e, const mb_head_loss* hl) {
+    if (!e || !hl) return MB_ERR_ARG;
+    return e->set_head_loss_ex(*hl, e->c.num_labels);
+}
+int mb_xlnet_get_head_loss_ex(const mb_xlnet_engine* e, mb_head_loss* hl, float* vec, int* has_vec) {
+    if (!e) return MB_ERR_ARG;
+    return e->get_head_loss_ex(hl, vec, has_vec);
+}
 int mb_xlnet_set_profiling(mb_xlnet_engine* e, int on) {
     if (!e) return MB_ERR_ARG;
     return e->set_profiling(on, e->c.n_layer);

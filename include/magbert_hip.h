@@ -179,6 +179,28 @@ int mb_head_forward(const float* z, const float* Wc, const float* bc, const floa
 int mb_head_backward(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale, const float* pooled,
                      const float* Wc, void* dz, float* dWc, float* dbc, float* dbp, void* zero_p, size_t zero_bytes, int B, int H,
                      int num_labels, const mb_dropkey* drop, int loss_kind, float loss_param, const float* loss_vec, void* stream);
+/* The objective with its options: the triple above plus label smoothing, a focal exponent and an ignored label.  All options zero =
+ * the triple alone, and the `_ex` entries then launch exactly what the entries above launch.
+ *   cross_entropy, q = softmax(x_b), kept = (y_b != ignore_index), W = sum over kept b of w[y_b] (w = 1 without weights: the count):
+ *     label_smoothing e in [0, 1):  [ (1-e) sum_kept w[y_b] (-log q_by) + (e/C) sum_kept sum_k w_k (-log q_bk) ] / W
+ *     focal_gamma g, 0 or finite and >= 1, not together with smoothing:  sum_kept w[y_b] (1 - q_by)^g (-log q_by) / W
+ *     has_ignore_index != 0: a label equal to ignore_index is left out of the loss, of W and of every gradient, even where it names
+ *     a class; the dz row of its sample is written as zeros
+ *     (torch.nn.functional.cross_entropy(weight, ignore_index, label_smoothing), with ONE deliberate departure: at W == 0 -- every
+ *     sample ignored, or every kept sample in a class of weight 0 -- the loss and all gradients are 0 where torch returns NaN, so
+ *     that no NaN reaches the AdamW moments)
+ *   bce: focal_gamma as above: mean of (1 - p_t)^g l, l = the bce term with its pos_weight, 1 - p_t = y sigmoid(-x) + (1-y) sigmoid(x)
+ * MB_ERR_ARG: e outside [0, 1), g not in {0} or [1, inf), both above 0, smoothing or an ignore_index on a kind other than
+ * cross_entropy, g on a kind other than cross_entropy or bce, a NULL struct.  Not built: 0 < g < 1, an alpha other than the weights,
+ * ignore_index for bce or the default kind, per-sample weights, reductions other than mean, a normaliser across data-parallel ranks
+ * (each rank normalises its own batch).
+ * vec: a DEVICE pointer for the two operator entries, a HOST pointer (copied) for the engines' setters. */
+typedef struct { int kind; float param; const float* vec; float label_smoothing; float focal_gamma; int has_ignore_index; int ignore_index; } mb_head_loss;
+int mb_head_forward_ex(const float* z, const float* Wc, const float* bc, const float* labels, float* pooled, float* logits, float* loss,
+                       float* loss_run, int B, int H, int num_labels, const mb_dropkey* drop, const mb_head_loss* hl, void* stream);
+int mb_head_backward_ex(int dtype, const float* dlogits, const float* logits, const float* labels, float loss_scale, const float* pooled,
+                        const float* Wc, void* dz, float* dWc, float* dbc, float* dbp, void* zero_p, size_t zero_bytes, int B, int H,
+                        int num_labels, const mb_dropkey* drop, const mb_head_loss* hl, void* stream);
 
 /* Multimodal Adaptation Gate, MAG.forward (modeling.py:25-51) and its adjoint, for T tokens.
  * Parameters in the REFERENCE layout: W_hv [H][V+H], W_ha [H][A+H], W_v [H][V], W_a [H][A], biases [H], LayerNorm [H].
@@ -329,6 +351,11 @@ int mb_bert_set_head_mask(mb_bert_engine* e, const float* head_mask);
  * get: what is set; vec (num_labels floats, may be NULL) is written only when *has_vec comes back 1. */
 int mb_bert_set_head_loss(mb_bert_engine* e, int kind, float param, const float* vec);
 int mb_bert_get_head_loss(const mb_bert_engine* e, int* kind, float* param, float* vec, int* has_vec);
+/* ... with the options of the mb_head_loss struct above (vec a HOST pointer, copied).  Sticky, legal between steps, checked before any device
+ * call (an engine without a device will do); a change drops the captured step and stage graphs.  mb_bert_set_head_loss sets the triple
+ * with every option cleared.  get: *hl receives what is set, its vec NULL; the vector goes to `vec` as in mb_bert_get_head_loss. */
+int mb_bert_set_head_loss_ex(mb_bert_engine* e, const mb_head_loss* hl);
+int mb_bert_get_head_loss_ex(const mb_bert_engine* e, mb_head_loss* hl, float* vec, int* has_vec);
 int mb_bert_set_inputs_embeds(mb_bert_engine* e, const float* inputs_embeds);
 /* position_ids (bert.py:211-216): int64 [B*L] device tensor of position-table rows for the next forwards / backwards, NULL =
  * BertEmbeddings' default arange(seq_len).  Sticky like head_mask; the single-call step refuses to run while it is set. */
@@ -582,6 +609,8 @@ int mb_xlnet_attention_probs_into(mb_xlnet_engine* e, int layer, float* out, voi
 int mb_xlnet_set_head_mask(mb_xlnet_engine* e, const float* head_mask);
 int mb_xlnet_set_head_loss(mb_xlnet_engine* e, int kind, float param, const float* vec);      /* as mb_bert_set_head_loss; the query-stream head has no loss */
 int mb_xlnet_get_head_loss(const mb_xlnet_engine* e, int* kind, float* param, float* vec, int* has_vec);
+int mb_xlnet_set_head_loss_ex(mb_xlnet_engine* e, const mb_head_loss* hl);                    /* as mb_bert_set_head_loss_ex */
+int mb_xlnet_get_head_loss_ex(const mb_xlnet_engine* e, mb_head_loss* hl, float* vec, int* has_vec);
 /* perm_mask / input_mask (xlnet.py:258-296): bytes [B][L][L] in device memory, sticky until reset with NULL; perm[b][i][j] != 0 <=>
  * data_mask[i, j, b] = input_mask[j, b] + perm_mask[i, j, b] > 0, i.e. query i may not attend to key j (i == j is always allowed:
  * non_tgt_mask, xlnet.py:288-296).  Combined with the attention_mask argument of the passes by OR.  Explicit forwards /

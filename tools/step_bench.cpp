@@ -22,12 +22,17 @@
 //            (mb_*_set_update_frozen): no weight-gradient launch for those layers, no embedding backward; composes with --layer_decay and
 //            --max_grad_norm.  Without --layer_decay the rest is the two parameter groups as a two-class map.  Prints mb_*_freeze_stats.
 //   --act gelu|relu|swish|silu|gelu_new|mish: the feed-forward activation (mb_bert_config.hidden_act / mb_xlnet_config.ff_activation)
-//   --loss default|mse|l1|smooth_l1 [--loss_beta X]: the head's objective (mb_*_set_head_loss; the run stays at num_labels = 1)
+//   --loss default|mse|l1|smooth_l1|bce|cross_entropy [--loss_beta X]: the head's objective (mb_*_set_head_loss_ex)
+//   --num_labels N: the head's width (default 1).  Labels are drawn to match: regression targets, class indices in [0, N) for the
+//            cross entropy (and the default kind at N > 1), {0, 1} targets for bce
+//   --loss_smoothing X, --loss_gamma X, --loss_ignore K: label smoothing, the focal exponent, ignore_index of mb_head_loss; with
+//            --loss_ignore every fifth sample carries the label K
 //   --inject N: MAG in front of encoder layer N (injection_index of either config; default 0 for MAG-BERT, 1 for MAG-XLNet)
 //   --h2d:   0 batch resident in HBM, 1 hipMemcpyAsync per step, 2 batch read in place from pinned host memory by the prologue
 //
 // Prints one line per run: ms/step (HIP events around the K timed steps), host enqueue ms/step, samples/s, final loss.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -56,6 +61,7 @@ int main(int argc, char** argv) {
     int all_live = 0;           // --all_live 1: every sample has L - 2 words (no padding token: the worst case of the live-row weight gradients)
     const char* act_name = "gelu";
     int loss_kind = MB_LOSS_DEFAULT; double loss_beta = 1.0; const char* loss_name = "default";
+    int num_labels = 1, loss_has_ignore = 0, loss_ignore = 0; double loss_smoothing = 0.0, loss_gamma = 0.0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--steps") steps = atoi(v); else if (k == "--warmup") warmup = atoi(v); else if (k == "--batch") B = atoi(v);
@@ -79,22 +85,27 @@ int main(int argc, char** argv) {
             act_name = v;
         }
         else if (k == "--loss") {
-            const char* names[] = {"default", "mse", "l1", "smooth_l1"};
+            const char* names[] = {"default", "mse", "l1", "smooth_l1", "bce", "cross_entropy"};
             loss_kind = -1;
-            for (int a = 0; a < 4; ++a) if (strcmp(v, names[a]) == 0) loss_kind = a;
-            if (loss_kind < 0) { fprintf(stderr, "--loss: default | mse | l1 | smooth_l1\n"); return 1; }
+            for (int a = 0; a < 6; ++a) if (strcmp(v, names[a]) == 0) loss_kind = a;
+            if (loss_kind < 0) { fprintf(stderr, "--loss: default | mse | l1 | smooth_l1 | bce | cross_entropy\n"); return 1; }
             loss_name = v;
         }
         else if (k == "--loss_beta") loss_beta = atof(v);
+        else if (k == "--num_labels") num_labels = atoi(v);
+        else if (k == "--loss_smoothing") loss_smoothing = atof(v);
+        else if (k == "--loss_gamma") loss_gamma = atof(v);
+        else if (k == "--loss_ignore") { loss_has_ignore = 1; loss_ignore = atoi(v); }
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --loss --loss_beta --inject --all_live)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --loss --loss_beta --num_labels --loss_smoothing --loss_gamma --loss_ignore --inject --all_live)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
     mb_bert_config c = {};
     c.vocab_size = 30522; c.hidden_size = hidden; c.num_layers = layers; c.num_heads = heads; c.intermediate_size = inter;
-    c.max_position = 512; c.type_vocab = 2; c.num_labels = 1; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
+    if (num_labels < 1) { fprintf(stderr, "--num_labels: at least 1\n"); return 1; }
+    c.max_position = 512; c.type_vocab = 2; c.num_labels = num_labels; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
     c.layer_norm_eps = 1e-12f; c.mag_layer_norm_eps = 1e-5f; c.beta_shift = 1.0f;
     c.hidden_dropout = 0.1f; c.attn_dropout = 0.1f; c.mag_dropout = 0.5f; c.dtype = dtype; c.max_batch = B; c.max_seq = L;
     c.hidden_act = act; c.injection_index = inject < 0 ? 0 : inject;
@@ -104,7 +115,7 @@ int main(int argc, char** argv) {
     if (xl) {
         if (!graph || dp) { fprintf(stderr, "--model xlnet: the single-call step only (--graph 1|2, no --dp)\n"); return 1; }
         mb_xlnet_config xc = {};
-        xc.vocab_size = 32000; xc.d_model = hidden; xc.n_layer = layers; xc.n_head = heads; xc.d_inner = inter; xc.num_labels = 1;
+        xc.vocab_size = 32000; xc.d_model = hidden; xc.n_layer = layers; xc.n_head = heads; xc.d_inner = inter; xc.num_labels = num_labels;
         xc.visual_dim = V; xc.acoustic_dim = A; xc.injection_index = inject < 0 ? 1 : inject;
         xc.layer_norm_eps = 1e-12f; xc.mag_layer_norm_eps = 1e-5f; xc.beta_shift = 1.0f;
         xc.dropout = 0.1f; xc.summary_last_dropout = 0.1f; xc.mag_dropout = 0.5f; xc.dtype = dtype; xc.max_batch = B; xc.max_seq = L;
@@ -117,10 +128,14 @@ int main(int argc, char** argv) {
         n = mb_bert_param_count(e); nd = mb_bert_decay_count(e); wsb = mb_bert_workspace_bytes(e);
         mb_bert_shadow_range(e, &shb, &she);
     }
-    if (loss_kind != MB_LOSS_DEFAULT) {
-        const float beta = loss_kind == MB_LOSS_SMOOTH_L1 ? (float)loss_beta : 0.f;
-        if (xl) MCK(mb_xlnet_set_head_loss(ex, loss_kind, beta, nullptr)); else MCK(mb_bert_set_head_loss(e, loss_kind, beta, nullptr));
+    if (loss_kind != MB_LOSS_DEFAULT || loss_smoothing != 0.0 || loss_gamma != 0.0 || loss_has_ignore) {
+        const mb_head_loss hlx = {loss_kind, loss_kind == MB_LOSS_SMOOTH_L1 ? (float)loss_beta : 0.f, nullptr, (float)loss_smoothing, (float)loss_gamma,
+                                  loss_has_ignore, loss_ignore};       // (an option the kind does not take: MB_ERR_ARG from the setter)
+        if (xl) MCK(mb_xlnet_set_head_loss_ex(ex, &hlx)); else MCK(mb_bert_set_head_loss_ex(e, &hlx));
     }
+    const bool per_element = loss_kind >= MB_LOSS_MSE && loss_kind <= MB_LOSS_BCE;      // labels [B][num_labels], else [B]
+    const bool class_labels = loss_kind == MB_LOSS_CROSS_ENTROPY || (loss_kind == MB_LOSS_DEFAULT && num_labels > 1);
+    const int lab_per = per_element ? num_labels : 1;
     float *P, *G, *M, *Vv; void *SH, *WS;
     HCK(hipMalloc(&P, n * 4)); HCK(hipMalloc(&G, n * 4)); HCK(hipMalloc(&M, n * 4)); HCK(hipMalloc(&Vv, n * 4));
     HCK(hipMalloc(&SH, n * 2)); HCK(hipMalloc(&WS, wsb));
@@ -145,7 +160,7 @@ int main(int argc, char** argv) {
 
     // synthetic batches (host pinned + device resident)
     const size_t T = (size_t)B * L;
-    const size_t bytes = T * 8 * 3 + T * V * 4 + T * A * 4 + (size_t)B * 4;
+    const size_t bytes = T * 8 * 3 + T * V * 4 + T * A * 4 + (size_t)B * lab_per * 4;
     std::vector<char*> hb(nbatch), db(nbatch);
     auto view = [&](char* p) { Batch b; b.ids = (int64_t*)p; b.seg = b.ids + T; b.mask = b.seg + T; b.vis = (float*)(b.mask + T);
                                b.aco = b.vis + T * V; b.lab = b.aco + T * A; return b; };
@@ -163,12 +178,17 @@ int main(int argc, char** argv) {
                 for (int j = 0; j < A; ++j) b.aco[((size_t)s * L + t) * A + j] = nrand();
             }
             b.ids[s * L + nw + 1] = 102; b.mask[s * L + nw + 1] = 1;
-            b.lab[s] = 6.f * urand() - 3.f;
+            for (int j = 0; j < lab_per; ++j) {
+                const float u = urand();
+                b.lab[(size_t)s * lab_per + j] = class_labels ? (float)std::min(num_labels - 1, (int)(u * num_labels))
+                                                 : loss_kind == MB_LOSS_BCE ? (u < 0.5f ? 0.f : 1.f) : 6.f * u - 3.f;
+            }
+            if (loss_has_ignore && s % 5 == 4) b.lab[s] = (float)loss_ignore;
         }
         HCK(hipMemcpy(db[k], hb[k], bytes, hipMemcpyHostToDevice));
     }
     float *logits, *loss;
-    HCK(hipMalloc(&logits, (size_t)B * 4)); HCK(hipMalloc(&loss, 8)); HCK(hipMemset(loss, 0, 8));
+    HCK(hipMalloc(&logits, (size_t)B * num_labels * 4)); HCK(hipMalloc(&loss, 8)); HCK(hipMemset(loss, 0, 8));
 
     mb_comm* comm = nullptr;
     if (dp) {
@@ -291,10 +311,14 @@ int main(int argc, char** argv) {
     float hl[2]; HCK(hipMemcpy(hl, loss, 8, hipMemcpyDeviceToHost));
     const double host_ms = std::chrono::duration<double, std::milli>(t1 - t0).count() / steps;
     const double wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count() / steps;
-    char shape[96] = "";
+    char shape[192] = "";
     if ((hidden != 768 || heads != 12 || inter != 3072)) snprintf(shape, sizeof shape, " hidden=%d heads=%d inter=%d", hidden, heads, inter);
     if (act != MB_ACT_GELU) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " act=%s", act_name);
     if (loss_kind != MB_LOSS_DEFAULT) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " loss=%s", loss_name);
+    if (num_labels != 1) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " num_labels=%d", num_labels);
+    if (loss_smoothing != 0.0) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " smoothing=%g", loss_smoothing);
+    if (loss_gamma != 0.0) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " gamma=%g", loss_gamma);
+    if (loss_has_ignore) snprintf(shape + strlen(shape), sizeof shape - strlen(shape), " ignore=%d", loss_ignore);
     printf("step_bench %sdtype=%s B=%d L=%d V=%d layers=%d%s graph=%d h2d=%d : %.3f ms/step (events) %.3f ms/step (wall) host-enqueue %.3f ms/step "
            "%.1f samples/s last-loss %.4f mean-loss %.4f\n",
            xl ? "model=xlnet " : "", dtype == MB_DT_BF16 ? "bf16" : "fp32", B, L, V, layers, shape, graph, h2d, ms / steps, wall_ms, host_ms, B * 1e3 / (ms / steps), hl[0],
