@@ -170,6 +170,11 @@ PROTOTYPES = {
     "mb_xlnet_mark_grads_zero": (_i, [_vp, _i]),
     "mb_bert_distrust_word_stamps": (_i, [_vp]),
     "mb_bert_word_skip_updates": (_sz, [_vp]),
+    "mb_bert_distrust_word_moments": (_i, [_vp]),
+    "mb_bert_word_moment_skip_updates": (_sz, [_vp]),
+    "mb_bert_word_moment_scans": (_sz, [_vp]),
+    "mb_debug_adamw_sweep": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _sz, C.c_uint32, _vp]),
+    "mb_debug_word_moments_scan": (_i, [_vp, _vp, _vp, _sz, _sz, C.c_uint32, C.c_uint32, _vp]),
     "mb_bert_materialize_grads": (_i, [_vp, _vp]),
     "mb_xlnet_materialize_grads": (_i, [_vp, _vp]),
     "mb_bert_grads_stale": (_i, [_vp]),

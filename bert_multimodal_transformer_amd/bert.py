@@ -334,6 +334,7 @@ class _Core(object):
                                              _lib.ptr(self.ws), nbytes))
             self.weights_dirty = True
             _lib.check(self._fn("mark_grads_zero")(self.handle, 1 if self._gz else 0))
+            self.distrust_word_moments()          # the moments outlive the engine; the new one has seen none of their rows
 
     def _tensor_table(self):
         out = []
@@ -466,6 +467,13 @@ class _Core(object):
         self._gz_version = self.grads._version     # torch-side writes into the buffer (or any `.grad` view of it) move this counter
         if self.handle is not None:
             _lib.check(self._fn("mark_grads_zero")(self.handle, 1 if known_zero else 0))
+
+    def distrust_word_moments(self):
+        """tells the engine that somebody else may have written into the Adam moments of the word table (an optimizer state that was
+        loaded, an optimizer step outside the single-call step, new moment tensors): its next single-call update reads them all
+        and proves the zero rows anew (include/magbert_hip.h: mb_bert_distrust_word_moments)"""
+        if self.kind == "bert" and self.handle is not None:
+            _lib.check(self.lib.mb_bert_distrust_word_moments(self.handle))
 
     def torch_wrote_grads(self):
         """True when something on the torch side (autograd accumulating another loss term into a `.grad` view, a hand edit) has

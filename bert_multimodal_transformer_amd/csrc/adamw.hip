@@ -20,7 +20,7 @@ __global__ void __launch_bounds__(256) adamw_range_kernel(float* __restrict__ p,
     if (dyn) a = *dyn;                  // replayed step graph: this step's lr / step size / gradient scale live in device memory
     const size_t per = ((n4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
     const size_t begin = (size_t)blockIdx.x * per + threadIdx.x, end = min(n4, (size_t)(blockIdx.x + 1) * per);
-    adam_span<NT>(p, g, m, v, shadow, begin, end, a, n_decay, sh_begin, sh_end, keep_begin, keep_end, zero_grad, false, WordSkip{}, 0u);
+    adam_span<NT>(p, g, m, v, shadow, begin, end, a, n_decay, sh_begin, sh_end, keep_begin, keep_end, zero_grad, false, false, WordSkip{}, 0u);
 }
 
 // scalar tail (n % 4 elements) -- only hit by stand-alone tensors, the engine's flat buffers are 64-aligned
@@ -117,6 +117,7 @@ __global__ void __launch_bounds__(256) adamw_sweep_kernel(float* __restrict__ p,
     const size_t vb = (size_t)blockIdx.x * per, ve = min(total4, vb + per);
     const bool skip_on = ws.stamp != nullptr && ws.state[1] != 0u;
     const uint32_t stamp_no = skip_on ? ws.state[0] : 0u;
+    const bool lazy_on = skip_on && ws.state[2] != 0u;          // (this step's moment verdict: kernels.h WordSkip)
 #pragma unroll 1
     for (int k = 0; k < R.clear_first; ++k) {
         const size_t off = R.start4[k], nxt = R.start4[k + 1];
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(256) adamw_sweep_kernel(float* __restrict__ p,
         const AdamArgs a = cls[R.slot[k]];
         const size_t base4 = (size_t)R.begin4[k] - off;          // quad index in the buffers = base4 + index in the laid-out pieces
         adam_span<NT>(p, g, m, v, shadow, base4 + lo + threadIdx.x, base4 + hi, a, ~(size_t)0, sh_begin, sh_end, keep_begin, keep_end, 1,
-                      skip_on, ws, stamp_no);
+                      skip_on, lazy_on, ws, stamp_no);
     }
 }
 

@@ -33,6 +33,23 @@ template <bool NT> __device__ __forceinline__ AdamQuad adam_load(const float* p,
     }
     return q;
 }
+// ... and the parameters alone of a quad whose moments are known to be +0.0f and whose gradient is +0.0f too (kernels.h WordSkip:
+// MB_STAMP_SEEN clear, state[2] set): adam_decay_store is the other half
+template <bool NT> __device__ __forceinline__ f32x4 adam_load_p(const float* p, size_t i) {
+    if constexpr (NT) return __builtin_nontemporal_load((const f32x4*)(p + i));
+    else return *(const f32x4*)(p + i);
+}
+// What adam_update_store does to such a quad: with g = m = v = +0.0f the moments come out +0.0f again and p - step_size * (0 / (0 + eps))
+// is p bit for bit (the host vouches for the scalars: engine_common.h StepMixin::lazy_scalars_ok), so only the decoupled decay is
+// left -- the same statement, contraction off -- and m, v and g are neither read nor written.
+template <bool NT> __device__ __forceinline__ void adam_decay_store(f32x4 qp, float* p, bf16* shadow, size_t i, float decay, size_t n_decay,
+                                                                    size_t sh_begin, size_t sh_end) {
+#pragma clang fp contract(off)
+    if (i < n_decay && decay > 0.f) qp -= decay * qp;
+    if constexpr (NT) __builtin_nontemporal_store(qp, (f32x4*)(p + i));
+    else *(f32x4*)(p + i) = qp;
+    if (shadow && i >= sh_begin && i < sh_end) store4(shadow + i, qp);
+}
 template <bool NT> __device__ __forceinline__ void adam_update_store(AdamQuad q, float* p, float* g, float* m, float* v, bf16* shadow, size_t i,
                                                                      const AdamArgs& a, float omb1, float omb2, float decay, size_t n_decay,
                                                                      size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, int zero_grad) {
@@ -64,33 +81,42 @@ template <bool NT> __device__ __forceinline__ void adam_update_store(AdamQuad q,
 // The update loop of adamw.hip's kernels: a 256-thread block walks quads [begin, end) of the buffers (`begin` is this thread's first
 // quad) with two quads of every stream in flight.  skip_on (kernels.h WordSkip): a quad of [ws.begin, ws.end) whose row carries no
 // stamp `stamp_no` gets g = +0.0f without the load and keeps the zero it has without the store; a wave may straddle two rows (768
-// floats = three waves of quads), which costs a divergent load.  A literal `false` folds all of that away.
+// floats = three waves of quads), which costs a divergent load.  lazy_on (with skip_on only): such a quad whose row does not carry
+// MB_STAMP_SEEN either -- the one table word tells both -- has zero moments: adam_load_p / adam_decay_store, 8 instead of 24 bytes per
+// parameter.  A literal `false` folds all of that away.
 // (The element index is formed inside the bounds check: hoisted above it, the single-range kernel takes 68 VGPRs instead of 62 and
 //  loses its eighth wave per SIMD -- tests/test_host_cpu.py::test_adamw_kernels_keep_their_residency.)
 template <bool NT>
 __device__ __forceinline__ void adam_span(float* p, float* g, float* m, float* v, bf16* shadow, size_t begin, size_t end, const AdamArgs& a,
                                           size_t n_decay, size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, int zero_grad,
-                                          bool skip_on, const WordSkip& ws, uint32_t stamp_no) {
+                                          bool skip_on, bool lazy_on, const WordSkip& ws, uint32_t stamp_no) {
     constexpr int UNR = 2; const size_t stride = 256;
     const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
     const float decay = a.lr * a.weight_decay;
     for (size_t i4 = begin; i4 < end; i4 += stride * UNR) {
         AdamQuad q[UNR];
-        bool live[UNR];
+        bool live[UNR], lazy[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            live[u] = true;
+            live[u] = true; lazy[u] = false;
             if (i4 + u * stride < end) {
                 const size_t i = (i4 + u * stride) * 4;
-                if (skip_on && i >= ws.begin && i < ws.end) live[u] = ws.stamp[(uint32_t)(i - ws.begin) / ws.row_len] == stamp_no;
-                q[u] = adam_load<NT>(p, g, m, v, i, live[u]);
+                if (skip_on && i >= ws.begin && i < ws.end) {
+                    const uint32_t w = ws.stamp[(uint32_t)(i - ws.begin) / ws.row_len];
+                    live[u] = (w & ~MB_STAMP_SEEN) == stamp_no;
+                    lazy[u] = lazy_on && !live[u] && !(w & MB_STAMP_SEEN);
+                }
+                if (lazy[u]) q[u].p = adam_load_p<NT>(p, i);
+                else q[u] = adam_load<NT>(p, g, m, v, i, live[u]);
             }
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
-            if (i4 + u * stride < end)
-                adam_update_store<NT>(q[u], p, g, m, v, shadow, (i4 + u * stride) * 4, a, omb1, omb2, decay, n_decay, sh_begin, sh_end, keep_begin,
-                                      keep_end, live[u] ? zero_grad : 0);
+            if (i4 + u * stride < end) {
+                if (lazy[u]) adam_decay_store<NT>(q[u].p, p, shadow, (i4 + u * stride) * 4, decay, n_decay, sh_begin, sh_end);
+                else adam_update_store<NT>(q[u], p, g, m, v, shadow, (i4 + u * stride) * 4, a, omb1, omb2, decay, n_decay, sh_begin, sh_end,
+                                           keep_begin, keep_end, live[u] ? zero_grad : 0);
+            }
     }
 }
 

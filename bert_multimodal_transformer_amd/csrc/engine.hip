@@ -205,10 +205,12 @@ static void build_layout(mb_bert_engine* e) {
     e->carve_step(w, T, (int)V, (int)A, c.max_batch, c.num_labels, SITE_LAYER0 + 4 * c.num_layers);
     e->idcnt_off = w.take((size_t)c.vocab_size * 4);          // token-id occurrence table of the single-call step (MB_EMBED_UNIQUE=0: off)
     e->idcnt_enable = env_on("MB_EMBED_UNIQUE", true);
-    // stamps of the word rows a step touched + the sweep's two state words (StepMixin::stamp_live; MB_ADAMW_SKIP_ZERO_ROWS=0: full read)
+    // stamps of the word rows a step touched (their top bit: the row's seen mark) + the sweep's three state words (StepMixin::stamp_live,
+    // mv_clean; MB_ADAMW_SKIP_ZERO_ROWS=0: full read, MB_ADAMW_SKIP_ZERO_MOMENTS=0: every row's moments are read and written)
     e->stamp_rows = (size_t)c.vocab_size;
-    e->stamp_off = w.take(((size_t)c.vocab_size + 2) * 4);
+    e->stamp_off = w.take(((size_t)c.vocab_size + 4) * 4);
     e->stamp_enable = env_on("MB_ADAMW_SKIP_ZERO_ROWS", true);
+    e->mv_enable = e->stamp_enable && env_on("MB_ADAMW_SKIP_ZERO_MOMENTS", true);
     // the live-row list of a batch + its count word (StepMixin::live_built; MB_WGRAD_LIVE_ROWS=0: dense weight gradients); bf16 only
     if (c.dtype == DT_BF16) {
         e->live_cap = std::max((size_t)192, T);
@@ -601,6 +603,27 @@ int mb_debug_mag_backward_ex(int dtype, const void* d_out, const void* text, con
     return MB_OK;
 }
 
+// Test hooks: the end-of-step sweep over a caller-built piece table (kernels.h AdamPieces: piece k = quads [begin4[k], begin4[k] + len4[k])
+// of the buffers with cls[slot[k]], no clear-only pieces), word range and tables -- everything device memory but the three piece arrays --
+// and the scan behind the seen marks.
+int mb_debug_adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, int npieces, const uint32_t* begin4, const uint32_t* len4,
+                         const uint8_t* slot, size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, const void* cls,
+                         const void* stamp, const void* state, size_t word_begin, size_t word_end, uint32_t row_len, void* stream) {
+    if (npieces < 0 || npieces > MB_SWEEP_PIECES_MAX || (npieces && (!begin4 || !len4 || !slot))) return MB_ERR_ARG;
+    AdamPieces r = {};
+    for (int k = 0; k < npieces; ++k) {
+        if ((uint64_t)r.start4[k] + len4[k] > 0xffffffffull) return MB_ERR_SHAPE;
+        r.begin4[k] = begin4[k]; r.slot[k] = slot[k]; r.start4[k + 1] = r.start4[k] + len4[k];
+    }
+    r.count = r.clear_first = npieces;
+    const WordSkip skip = {(const uint32_t*)stamp, (const uint32_t*)state, word_begin, word_end, row_len};
+    return adamw_sweep(p, g, m, v, shadow, r, sh_begin, sh_end, keep_begin, keep_end, (const AdamArgs*)cls, skip, (hipStream_t)stream);
+}
+int mb_debug_word_moments_scan(const float* m, const float* v, void* stamp, size_t begin, size_t rows, uint32_t row_len, uint32_t keep_no,
+                               void* stream) {
+    return word_moments_scan(m, v, (uint32_t*)stamp, begin, rows, row_len, keep_no, (hipStream_t)stream);
+}
+
 int mb_adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, size_t n_decay, size_t sh_begin,
                   size_t sh_end, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   int correct_bias, float grad_scale, int zero_grad, void* stream) {
@@ -682,6 +705,7 @@ int mb_bert_bind(mb_bert_engine* e, float* params, float* grads, void* shadow, v
     e->grads_zero = false;                 // a newly bound gradient buffer: nothing is known about its contents
     e->frz_dirty = true;
     e->stamp_live = e->word_zero = false; e->sweep_no = 1;      // (and a workspace that is cleared before its first pass)
+    e->mv_clean = e->mv_prev_single = false;
     e->ws_zeroed = false; e->padT = -1;
     e->drop_graphs();                         // captured against the old buffers
     char* mws = e->ws + e->ws_mag;
@@ -1335,6 +1359,13 @@ int mb_bert_distrust_word_stamps(mb_bert_engine* e) {
     return MB_OK;
 }
 size_t mb_bert_word_skip_updates(const mb_bert_engine* e) { return e ? e->skip_updates : 0; }
+int mb_bert_distrust_word_moments(mb_bert_engine* e) {
+    if (!e) return MB_ERR_ARG;
+    e->distrust_word_moments();
+    return MB_OK;
+}
+size_t mb_bert_word_moment_skip_updates(const mb_bert_engine* e) { return e ? e->mv_updates : 0; }
+size_t mb_bert_word_moment_scans(const mb_bert_engine* e) { return e ? e->mv_scans : 0; }
 int mb_bert_materialize_grads(mb_bert_engine* e, void* stream) {
     if (!e) return MB_ERR_ARG;
     return e->materialize_grads(e->G, (hipStream_t)stream);

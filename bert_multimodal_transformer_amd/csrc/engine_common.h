@@ -272,8 +272,8 @@ struct StepMixin {
     uint32_t* cls_rows(char* ws) const { return live_rows(ws) + live_cap + 8; }
     uint32_t* cls_count(char* ws) const { return cls_rows(ws) + live_cap; }
     // Untouched word rows (kernels.h WordSkip; MB_ADAMW_SKIP_ZERO_ROWS=0: off).  stamp_off: workspace offset of the vocab-sized stamp table
-    // followed by the two state words (0 = this engine has none); sweep_no: the number of the next optimizer update, counted on the host
-    // (train_step_impl runs for every step, replayed or not) and never 0, the table's initial value.
+    // followed by the three state words (0 = this engine has none); sweep_no: the number of the next optimizer update, counted on the host
+    // (train_step_impl runs for every step, replayed or not), never 0, the table's initial value, and below MB_STAMP_SEEN.
     // stamp_live is the proof the sweep needs: "every word-row gradient was +0.0f at some point, and every backward since then belonged
     // to a single-call step whose prologue stamped its batch with sweep_no".  word_zero is the first half: set only by the engine's own
     // single-call step that ended with the optimizer (its sweep covers the word table and stores the zeros); a caller's claim
@@ -284,6 +284,34 @@ struct StepMixin {
     size_t stamp_off = 0, stamp_rows = 0; bool stamp_enable = false, stamp_live = false, word_zero = false;
     uint32_t sweep_no = 1;
     size_t skip_updates = 0;       // updates enqueued with the proof in hand (mb_*_word_skip_updates: what the tests look at)
+    // Zero moments (kernels.h WordSkip state[2], MB_STAMP_SEEN; MB_ADAMW_SKIP_ZERO_MOMENTS=0, or the switch above off: off).  mv_clean is
+    // the proof the short path needs: "every word row without the seen mark holds +0.0f in m and v of the buffers (mv_m, mv_v)".  Only
+    // word_moments_scan proves it -- the moments are the caller's buffers, a fresh optimizer's too -- and it stays true while every
+    // update of the word table is a single-call one made with stamp_live: the prologue marks the rows of its batches, every other row
+    // gets g = +0.0f, and zero moments stay zero.  Withdrawn by any other update that may write those moments (the first one of a
+    // window, a data-parallel or stage-driven step, a failed step), by what withdraws stamp_live for buffer reasons (a newly bound
+    // buffer, a change of frozen marks), by other moment buffers, and by mb_*_distrust_word_moments (the Python mirror: torch wrote
+    // into m or v, or updated the range itself).  The scan runs in front of the prologue of a step that could use the verdict and
+    // lacks only the proof, provided the previous update was a single-call one too (mv_prev_single): a caller that alternates paths
+    // never pays a scan per step.  mv_updates / mv_scans: updates enqueued with the verdict set, scans enqueued (what the tests look at).
+    bool mv_enable = false, mv_clean = false, mv_prev_single = false;
+    const float* mv_m = nullptr; const float* mv_v = nullptr;
+    size_t mv_updates = 0, mv_scans = 0;
+    void distrust_word_moments() { mv_clean = false; }
+    // the short path has the same bits: with g = m = v = +0.0f these scalars give m = v = +0.0f again and p - step_size * (0 / eps) == p
+    // bit for bit (no NaN out of 0 * inf, no -0.0f out of a negative factor that would turn a p of -0.0f into +0.0f)
+    static bool lazy_scalars_ok(const AdamArgs& a) {
+        const float d = a.lr * a.weight_decay;
+        return a.eps > 0.f && std::isfinite(a.step_size) && a.step_size >= 0.f && std::isfinite(d) && std::isfinite(a.beta1) && a.beta1 >= 0.f &&
+               std::isfinite(a.beta2) && a.beta2 >= 0.f && std::isfinite(a.grad_scale) && a.grad_scale >= 0.f;
+    }
+    // ... in every slot that covers [b, e) -- the word table -- of this step's update (pa: the prologue's scalars, filled)
+    bool lazy_slots_ok(const PrologueArgs& pa, size_t b, size_t e, size_t n_decay) const {
+        if (n_classes == 0) return (b >= n_decay || lazy_scalars_ok(pa.adam[0])) && (e <= n_decay || lazy_scalars_ok(pa.adam[1]));
+        for (size_t s = 0; s + 1 < seg_bounds.size(); ++s)
+            if (seg_bounds[s] < e && seg_bounds[s + 1] > b && !lazy_scalars_ok(pa.cls[seg_class[s]])) return false;
+        return true;
+    }
     uint32_t* stamp_table(char* ws) const { return (uint32_t*)(ws + stamp_off); }
     uint32_t* stamp_state(char* ws) const { return stamp_table(ws) + stamp_rows; }
     // the unclassed end-of-step sweep as ONE launch over its up-to-three ranges (dp_step.h enqueue_update); false: one launch per range.
@@ -407,6 +435,7 @@ struct StepMixin {
         struct Scope { StepMixin* m; ~Scope() { m->dyn = false; m->capturing = false; m->in_step = false; m->stage_mode = false; } } scope{this};
         dyn = true; in_step = true; stage_mode = true;
         stamp_live = word_zero = false;      // (the stage-driven step's prologue stamps nothing)
+        mv_clean = mv_prev_single = false;   // (and its update reads no seen mark)
         frz_dirty = true;                    // (and its backward ignores the frozen marks)
         if (mode == 2) return enqueue(st);
         StageGraph* g = nullptr;
@@ -569,7 +598,7 @@ struct StepMixin {
     }
     // a change of frozen marks: what used to be frozen may hold anything a fused kernel wrote, what becomes frozen may hold a gradient --
     // the next single-call step clears the frozen ranges first; and the word-row stamps prove nothing about a table that was left out
-    void marks_changed() { frz_dirty = true; stamp_live = word_zero = false; }
+    void marks_changed() { frz_dirty = true; stamp_live = word_zero = false; mv_clean = false; }
     int set_update_frozen(int ns, const uint8_t* frozen) {
         if (n_classes == 0) return MB_ERR_MODE;          // marks belong to a map
         if (ns != (int)seg_class.size() || !frozen) return MB_ERR_ARG;
@@ -851,7 +880,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     const bool stale_before = e->grads_stale;
     // what the step leaves behind is only known once everything was enqueued: an early error return leaves "nothing known"
     struct Flags {
-        E* e; bool ok, with_opt, stale_before;
+        E* e; bool ok, with_opt, stale_before, single, lazy;
         ~Flags() {
             e->in_step = false; e->loss_cleared = false; e->packed = false; e->packed_w = false; e->counted = false; e->live_built = false;
             if (ok && e->clip_step) e->clip_ran = true;
@@ -860,11 +889,15 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
             e->grads_stale = ok ? (with_opt && e->keep_in_step()) : stale_before;
             // an update was enqueued: its sweep left every word gradient zero, and the next batch is stamped with the next number
             if (ok && with_opt && e->stamp_live) ++e->skip_updates;
+            // ... and the zero moments of unmarked word rows zero only if it was a single-call update with that proof (StepMixin::mv_clean)
+            if (!ok || (with_opt && !(e->stamp_live && single))) e->mv_clean = false;
+            if (ok && with_opt && lazy) ++e->mv_updates;
+            if (with_opt) e->mv_prev_single = ok && single;
             if (!ok || with_opt) e->stamp_live = false;
             e->word_zero = ok && with_opt;
-            if (ok && with_opt && ++e->sweep_no == 0u) e->sweep_no = 1u;
+            if (ok && with_opt && ++e->sweep_no >= MB_STAMP_SEEN) e->sweep_no = 1u;      // (the top bit of a stamp word is the seen mark)
         }
-    } flags{e, false, m != nullptr, stale_before};
+    } flags{e, false, m != nullptr, stale_before, variant <= 0, false};
     // untouched word rows (StepMixin::stamp_live): this step's prologue stamps its batch, so a window that is live stays live, and
     // word gradients the engine itself left all zero open one
     // (frozen marks: a step without an embedding backward has nobody to consume -- and clear -- the count table, and no sweep piece over
@@ -888,6 +921,7 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
     if (e->idcnt_enable && ids && !no_embed) { pa.ids = (const int64_t*)ids; pa.n_ids = B * L; pa.id_count = (int*)(ws + e->idcnt_off); }
     e->counted = pa.id_count != nullptr;
     if (stamping) { pa.stamp = e->stamp_table(ws); pa.stamp_state = e->stamp_state(ws); pa.stamp_no = e->sweep_no; pa.stamp_on = e->stamp_live ? 1u : 0u; }
+    if (stamping && e->mv_enable) pa.stamp_seen = MB_STAMP_SEEN;
     // live token rows for the weight gradients (not the data-parallel variants: they stay dense)
     if (e->live_off != 0 && e->live_enable && variant <= 0 && mask != nullptr && (size_t)align_up((size_t)B * L, 64) <= e->live_cap &&
         B <= MB_LIVE_MAX_SAMPLES && B * L <= MB_LIVE_MAX_ROWS) {
@@ -918,6 +952,21 @@ inline int train_step_impl(E* e, char* ws, int V, int A, int num_labels, const v
         if (e->n_classes > 0) { pa.ncls = e->n_classes; pa.cls_dst = e->class_state(ws); }
         if (clip) { pa.clip[0] = e->clip_max; pa.clip[1] = grad_scale; pa.clip_dst = e->clip_params(); }
     }
+    // zero moments (StepMixin::mv_clean): the verdict of this step's sweep, and the scan that proves it where only the proof is missing
+    // (on the step's stream in front of the prologue, which marks this batch's rows; never captured).  A clipping step reads every
+    // moment -- its grad_scale is a device value -- and keeps the proof; a frozen word table has no update piece to shorten.
+    if (m && v && (m != e->mv_m || v != e->mv_v)) { e->mv_clean = false; e->mv_m = m; e->mv_v = v; }
+    if (m && v && e->mv_enable && stamping && e->stamp_live && variant <= 0 && !clip) {
+        const WordSkip wsk = e->word_skip(ws);
+        if (wsk.stamp && wsk.end > wsk.begin && !e->range_frozen(wsk.begin, wsk.end) && e->lazy_slots_ok(pa, wsk.begin, wsk.end, e->n_decay)) {
+            if (!e->mv_clean && e->mv_prev_single) {
+                CK(word_moments_scan(m, v, e->stamp_table(ws), wsk.begin, (wsk.end - wsk.begin) / wsk.row_len, wsk.row_len, e->sweep_no, st));
+                e->mv_clean = true; ++e->mv_scans;
+            }
+            flags.lazy = e->mv_clean;
+        }
+    }
+    pa.stamp_lazy = flags.lazy ? 1u : 0u;
     CK(step_prologue(pa, st));
     if (mode == 2 || force_launches) {
         e->dyn = true;

@@ -333,6 +333,12 @@ int adamw_step(float* p, float* g, float* m, float* v, void* shadow, size_t n, s
 // backward feeds this update saw `row` in its batch (PrologueArgs::stamp).  When state[1] != 0 the engine vouches that every other row
 // of [begin, end) -- rows of `row_len` elements -- holds g == +0.0f: the sweep neither loads that gradient nor stores the zero back,
 // and runs the same arithmetic on a +0.0f it makes up.  state[1] == 0: the full read (decided per step, so a replayed graph obeys it).
+// Zero moments (MB_ADAMW_SKIP_ZERO_MOMENTS): the top bit of a stamp word is the row's `seen` mark -- set <=> the row may hold non-zero
+// moments (the prologue sets it with every stamp, word_moments_scan derives it from m and v); update numbers stay below it.  When
+// state[2] != 0 the engine vouches that every row without the mark holds m == v == +0.0f and that this step's scalars leave such a
+// row's moments and -- but for the decay -- its parameters bit for bit alone: an untouched row without the mark gets the decay only,
+// and neither m, v nor g of it is read or written.  state[2] == 0: the moments of every row are read and written.
+#define MB_STAMP_SEEN 0x80000000u
 struct WordSkip { const uint32_t* stamp; const uint32_t* state; size_t begin, end; uint32_t row_len; };
 // The end-of-step sweep of a single-call step as ONE launch over a table of pieces of the flat buffers (one adamw_step per range
 // otherwise).  Everything is ABSOLUTE here: p / g / m / v / shadow are the buffers' first elements, the shadow and keep ranges element
@@ -400,7 +406,8 @@ struct PrologueArgs {
     const int64_t* ids; int n_ids; int* id_count;     // id_count[ids[i]] += 1 (see embed_ln_backward), may be null
     // stamp[ids[i]] = stamp_no, the number of the optimizer update that will consume this batch's gradients, and stamp_state[0 .. 1] =
     // {stamp_no, stamp_on} for the sweep of that update (WordSkip above); never cleared, right under graph replay.  May be null
-    uint32_t* stamp; uint32_t* stamp_state; uint32_t stamp_no, stamp_on;
+    // stamp_seen (0 or MB_STAMP_SEEN) is or-ed into every stamp stored, stamp_state[2] = stamp_lazy (the moment verdict)
+    uint32_t* stamp; uint32_t* stamp_state; uint32_t stamp_no, stamp_on, stamp_seen, stamp_lazy;
     // the live token rows of this batch for the gathered weight gradients (GroupedGemmArgs::rows), built by ONE extra block from the
     // mask the launch gathers: live_rows[0 .. n) = the rows r < live_T (<= MB_LIVE_MAX_ROWS) with live_mask[r] != 0, the first row b * live_L
     // of EVERY sample (the [CLS] row the head reads: it carries a gradient whatever its mask word), and ALL rows of a sample (live_L
@@ -420,6 +427,11 @@ struct PrologueArgs {
 };
 static_assert(sizeof(PrologueArgs) <= 2048, "PrologueArgs travels as kernel arguments (4 KB limit)");
 int step_prologue(const PrologueArgs& a, hipStream_t st);
+// The proof behind WordSkip's state[2]: one wave per row of m / v[begin + row * row_len ...) (rows of row_len floats, multiples of 4,
+// 16-byte aligned) sets or clears MB_STAMP_SEEN of stamp[row] -- set <=> any bit of the row's m or v is set -- and keeps the stamp's number.
+// A row stamped `keep_no` is left as it is: a micro-step of the update still to come touched it, its moments are about to change.
+int word_moments_scan(const float* m, const float* v, uint32_t* stamp, size_t begin, size_t rows, uint32_t row_len, uint32_t keep_no,
+                      hipStream_t st);
 // p[0, bytes) = 0 as a kernel launch (bytes and p multiples of 4); up to MB_ZERO_MAX ranges in one launch
 #define MB_ZERO_MAX 8
 struct ZeroRanges {

@@ -872,8 +872,8 @@ __global__ void __launch_bounds__(256) step_prologue_kernel(const PrologueArgs a
         for (size_t i = tid; i < (size_t)a.n_ids; i += nth) atomicAdd(a.id_count + a.ids[i], 1);
     // ... and which word rows the coming optimizer update will find a gradient in (kernels.h WordSkip: every writer stores the same number)
     if (a.stamp != nullptr) {
-        for (size_t i = tid; i < (size_t)a.n_ids; i += nth) a.stamp[a.ids[i]] = a.stamp_no;
-        if (tid < 2) a.stamp_state[tid] = tid == 0 ? a.stamp_no : a.stamp_on;
+        for (size_t i = tid; i < (size_t)a.n_ids; i += nth) a.stamp[a.ids[i]] = a.stamp_no | a.stamp_seen;
+        if (tid < 3) a.stamp_state[tid] = tid == 0 ? a.stamp_no : tid == 1 ? a.stamp_on : a.stamp_lazy;
     }
     for (int k = 0; k < a.npack; ++k) {          // (before the copies: these loads cross PCIe too and should be in flight with them)
         const PrologueArgs::PackJob& j = a.pack[k];
@@ -967,6 +967,34 @@ int step_prologue(const PrologueArgs& a, hipStream_t st) {
         grid += 1;                                  // the LAST block builds the live-row list
     }
     hipLaunchKernelGGL(step_prologue_kernel, dim3(grid), dim3(256), 0, st, b);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ which word rows hold non-zero moments
+// (kernels.h word_moments_scan) one wave per row, four rows per block: a row's m and v as 16-byte words, or-ed together
+__global__ void __launch_bounds__(256) word_moments_scan_kernel(const float* __restrict__ m, const float* __restrict__ v,
+                                                                uint32_t* __restrict__ stamp, size_t rows, uint32_t row_len, uint32_t keep_no) {
+    const size_t row = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const u32x4* mr = (const u32x4*)(m + row * row_len);
+    const u32x4* vr = (const u32x4*)(v + row * row_len);
+    uint32_t any = 0u;
+    for (uint32_t i = lane; i < row_len / 4; i += 64) {
+        const u32x4 a = __builtin_nontemporal_load(mr + i), b = __builtin_nontemporal_load(vr + i);
+        any |= a[0] | a[1] | a[2] | a[3] | b[0] | b[1] | b[2] | b[3];
+    }
+    const bool nz = __ballot(any != 0u) != 0ull;
+    if (lane == 0) {
+        const uint32_t w = stamp[row];
+        if ((w & ~MB_STAMP_SEEN) != keep_no) stamp[row] = (w & ~MB_STAMP_SEEN) | (nz ? MB_STAMP_SEEN : 0u);
+    }
+}
+int word_moments_scan(const float* m, const float* v, uint32_t* stamp, size_t begin, size_t rows, uint32_t row_len, uint32_t keep_no, hipStream_t st) {
+    if (!m || !v || !stamp || row_len == 0 || (row_len | begin) % 4 || (((uintptr_t)m | (uintptr_t)v) & 15)) return MB_ERR_ARG;
+    if (rows == 0) return MB_OK;
+    if ((rows + 3) / 4 > 0x7fffffffull) return MB_ERR_SHAPE;
+    hipLaunchKernelGGL(word_moments_scan_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, m + begin, v + begin, stamp, rows, row_len, keep_no);
     return (int)hipGetLastError();
 }
 

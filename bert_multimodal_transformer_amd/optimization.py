@@ -27,6 +27,14 @@ UPDATE_CLASSES_MAX = 32
 UPDATE_SEGMENTS_MAX = 128
 
 
+def _distrust_word_moments(core):
+    """the Adam moments of `core`'s flat buffer are about to be written from here (bert._Core.distrust_word_moments: the engine's single-call
+    step keeps a proof about the word rows whose moments are zero; new moment tensors it notices itself, by their address)"""
+    fn = getattr(core, "distrust_word_moments", None)
+    if fn is not None:
+        fn()
+
+
 FROZEN = -1          # the class plan_*_segments(..., frozen=True) gives a segment no parameter group holds
 
 
@@ -478,6 +486,7 @@ class AdamW(torch.optim.Optimizer):
         self._t += 1
         for core, _ in self._covers.values():        # gradients a fused step left "logically zero" become real zeros before they are read
             core.materialize_grads()
+            _distrust_word_moments(core)             # this update writes the moments of every row it covers
         dp = self._dp
         late = []
         if dp is not None and getattr(dp, "late_ranges", None):
@@ -605,6 +614,7 @@ class AdamW(torch.optim.Optimizer):
             for c, st in zip(cores, extra["flat"]):
                 c._adam_m.copy_(st["exp_avg"])
                 c._adam_v.copy_(st["exp_avg_sq"])
+                _distrust_word_moments(c)
 
     def zero_grad(self, set_to_none=False):
         if self._plan is None:

@@ -103,6 +103,19 @@ int mb_debug_gemm_grouped_rows(int dtype, int count, const int* M, const int* N,
                                const void* const* rows, const void* const* nrows, void* stream);
 int mb_debug_live_rows(const int64_t* mask, int B, int L, int Tp, void* live_rows, void* live_count, void* cls_rows, void* cls_count,
                        void* stream);
+/* mb_debug_adamw_sweep: the end-of-step sweep of mb_bert_train_step over a caller-built table: piece k = quads [begin4[k], begin4[k] + len4[k])
+ *   of the flat buffers with the scalars cls[slot[k]] (cls: device, 7 floats per slot: lr, beta1, beta2, eps, weight_decay, step_size,
+ *   grad_scale); shadow / keep ranges and the word range [word_begin, word_end) in elements (multiples of 4), rows of row_len elements.
+ *   stamp (device uint32 per row; top bit = the row's seen mark, the rest the number of the update that touched it) and state (device, three
+ *   uint32: this update's number, the gradient verdict, the moment verdict); stamp == NULL: a plain sweep.  Nothing is checked against
+ *   the buffers' sizes.
+ * mb_debug_word_moments_scan: sets or clears the seen mark of stamp[row], row < rows, from m and v[begin + row * row_len ...); rows whose
+ *   number is keep_no are left alone. */
+int mb_debug_adamw_sweep(float* p, float* g, float* m, float* v, void* shadow, int npieces, const uint32_t* begin4, const uint32_t* len4,
+                         const uint8_t* slot, size_t sh_begin, size_t sh_end, size_t keep_begin, size_t keep_end, const void* cls,
+                         const void* stamp, const void* state, size_t word_begin, size_t word_end, uint32_t row_len, void* stream);
+int mb_debug_word_moments_scan(const float* m, const float* v, void* stamp, size_t begin, size_t rows, uint32_t row_len, uint32_t keep_no,
+                               void* stream);
 
 /* `count` (<= 4) weight gradients dW_g[M_g][N_g] += dY_g[K][M_g]^T X_g[K][N_g] in ONE launch (fp32 accumulate) -- the
  * four torch.nn.Linear weight gradients autograd produces per BertLayer (mm_backward under loss.backward(),
@@ -384,6 +397,20 @@ int mb_bert_mark_grads_zero(mb_bert_engine* e, int known_zero);
  * MB_ADAMW_SKIP_ZERO_ROWS=0 disables the skip; never needed when the host does not touch the buffer. */
 int mb_bert_distrust_word_stamps(mb_bert_engine* e);
 size_t mb_bert_word_skip_updates(const mb_bert_engine* e);      /* updates whose sweep was allowed to skip, since the engine was created */
+/* Zero moments of never-touched word rows.  Such a row's m and v are +0.0f and stay +0.0f, and its parameters change by the decoupled
+ * decay alone: under the skip above the sweep also leaves m, v and g of it unread and unwritten (8 instead of 24 bytes per parameter),
+ * when the engine can prove the moments zero.  The proof is a one-off scan of the word range of the moment buffers handed to
+ * mb_bert_train_step (one read, enqueued on the step's stream in front of a step that could use it); it holds while every update of
+ * the word table is a single-call update with the gradient proof above, on the same m and v.  The engine notices its own other
+ * updates (data-parallel, stage-driven, failed), new buffers and changed frozen marks; a host that WRITES INTO m OR v of the word
+ * table by any other way (loading an optimizer state, an optimizer step of its own, mb_adamw_step over the range) calls
+ * mb_bert_distrust_word_moments before the next single-call step, which then scans again.  Steps whose scalars would not leave the
+ * bits alone (eps <= 0, a non-finite or negative step size, beta or gradient scale, non-finite lr * weight_decay in a slot that
+ * covers the table), clipping steps and a frozen word table run the full path.  MB_ADAMW_SKIP_ZERO_MOMENTS=0 -- or
+ * MB_ADAMW_SKIP_ZERO_ROWS=0 -- disables it: no scan, every moment read and written. */
+int mb_bert_distrust_word_moments(mb_bert_engine* e);
+size_t mb_bert_word_moment_skip_updates(const mb_bert_engine* e);      /* updates enqueued with the moment skip in force */
+size_t mb_bert_word_moment_scans(const mb_bert_engine* e);             /* scans enqueued, since the engine was created */
 /* Lazy zeroing.  The zeros mb_bert_train_step's AdamW would write over the layers' GEMM weight gradients are only ever
  * overwritten by the next backward, so a step that ends with the optimizer leaves that range "logically zero, physically stale"
  * (the rest of the buffer IS zeroed).  The engine writes the zeros itself before any of its own backwards that accumulates;

@@ -8,6 +8,7 @@
 //              [--hidden H] [--heads n] [--inter I]       (both models; bert-large-uncased / xlnet-large-cased = --layers 24 --hidden 1024
 //                                                          --heads 16 --inter 4096; --heads defaults to H / 64, --inter to 4 H)
 //              [--graph 0|1|2] [--h2d 0|1|2] [--nbatch n] [--dp 0|1] [--wire fp32|bf16] [--sparse 0|1] [--timing 0|1] [--shard 0|1]
+//              [--vocab n]   (MAG-BERT: a word table of n rows, ids folded into it -- with a small one every row is touched)
 //   --dp 1:  the data-parallel step, mb_bert_train_step_dp, with a ONE-rank RCCL communicator created here through the C ABI
 //            (mb_comm_unique_id / mb_comm_create_rccl): the N > 1 code path -- graph chain, comm stream, events, ncclAllReduce /
 //            ncclAllGather calls, the row-wise word-embedding exchange -- without a second GPU.  Needs --graph 1|2.
@@ -58,6 +59,7 @@ int main(int argc, char** argv) {
     int dp = 0, wire = MB_DT_F32, sparse = 1, timing = 0, shard = 0, xl = 0, hidden = 768, heads = 0, inter = 0;
     double layer_decay = 1.0, head_lr_mult = 1.0, max_grad_norm = 0.0;
     int freeze_layers = 0, freeze_emb = 0, act = MB_ACT_GELU, inject = -1;      // --inject N: MAG in front of layer N (default: 0 | MAG-XLNet: 1)
+    int vocab_rows = 30522;     // --vocab n: a smaller word table, every id folded into it (every row of a small one is touched within a few batches)
     int all_live = 0;           // --all_live 1: every sample has L - 2 words (no padding token: the worst case of the live-row weight gradients)
     const char* act_name = "gelu";
     int loss_kind = MB_LOSS_DEFAULT; double loss_beta = 1.0; const char* loss_name = "default";
@@ -77,6 +79,7 @@ int main(int argc, char** argv) {
         else if (k == "--freeze_layers") freeze_layers = atoi(v); else if (k == "--freeze_emb") freeze_emb = atoi(v);
         else if (k == "--inject") inject = atoi(v);
         else if (k == "--all_live") all_live = atoi(v);
+        else if (k == "--vocab") vocab_rows = atoi(v);      // MAG-BERT: rows of the word table (ids are folded into them; >= 103)
         else if (k == "--act") {
             const char* names[] = {"gelu", "relu", "swish", "gelu_new", "mish"};
             act = strcmp(v, "silu") == 0 ? MB_ACT_SWISH : -1;
@@ -98,12 +101,12 @@ int main(int argc, char** argv) {
         else if (k == "--loss_ignore") { loss_has_ignore = 1; loss_ignore = atoi(v); }
         else if (k == "--wire") wire = strcmp(v, "bf16") == 0 ? MB_DT_BF16 : MB_DT_F32;
         else { fprintf(stderr, "unknown option %s (options: --model --steps --warmup --batch --seq --dtype --visual --layers --hidden --heads --inter "
-                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --loss --loss_beta --num_labels --loss_smoothing --loss_gamma --loss_ignore --inject --all_live)\n", k.c_str()); return 1; }
+                               "--graph --h2d --nbatch --dp --wire --sparse --timing --shard --layer_decay --head_lr_mult --max_grad_norm --freeze_layers --freeze_emb --act --loss --loss_beta --num_labels --loss_smoothing --loss_gamma --loss_ignore --inject --all_live --vocab)\n", k.c_str()); return 1; }
     }
     if (heads <= 0) heads = hidden / 64;
     if (inter <= 0) inter = 4 * hidden;
     mb_bert_config c = {};
-    c.vocab_size = 30522; c.hidden_size = hidden; c.num_layers = layers; c.num_heads = heads; c.intermediate_size = inter;
+    c.vocab_size = vocab_rows; c.hidden_size = hidden; c.num_layers = layers; c.num_heads = heads; c.intermediate_size = inter;
     if (num_labels < 1) { fprintf(stderr, "--num_labels: at least 1\n"); return 1; }
     c.max_position = 512; c.type_vocab = 2; c.num_labels = num_labels; c.visual_dim = V; c.acoustic_dim = A; c.pad_token_id = 0;
     c.layer_norm_eps = 1e-12f; c.mag_layer_norm_eps = 1e-5f; c.beta_shift = 1.0f;
@@ -173,7 +176,7 @@ int main(int argc, char** argv) {
             const int nw = all_live ? L - 2 : nw_drawn;
             b.ids[s * L] = 101; b.mask[s * L] = 1;
             for (int t = 1; t <= nw; ++t) {
-                b.ids[s * L + t] = 1000 + (int64_t)(rnd() % 29522); b.mask[s * L + t] = 1;
+                b.ids[s * L + t] = (1000 + (int64_t)(rnd() % 29522)) % (xl ? 32000 : vocab_rows); b.mask[s * L + t] = 1;
                 for (int j = 0; j < V; ++j) b.vis[((size_t)s * L + t) * V + j] = nrand();
                 for (int j = 0; j < A; ++j) b.aco[((size_t)s * L + t) * A + j] = nrand();
             }
